@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: CosyVoice2-0.5B-EU zero-shot synthesis throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 (default): a "step" = ONE utterance of BASELINE configs[1] (zero-shot FR, batch 1, bf16 weights, non-streaming) through the
   PRODUCT call `CosyVoice2Model.tts()` — scheduler, LLM prefill + autoregressive decode with the RAS sampler, flow encoder + 10
   Euler steps with CFG, HiFT vocoder, and the device->host copy of the waveform.  Inputs (text ids, prompt speech tokens, prompt
   mel, speaker embedding) are resident in HBM before the timed region.  Weights are synthetic at the real shapes (no checkpoints
-  offline), decode length forced to 250 tokens = 10 s of audio.  The same run also measures, as `extra`:
+  offline), decode length forced to 250 tokens = 10 s of audio.  With --full the same run also measures, as `extra`:
   configs[2] (32 concurrent calls coalesced into one batch, FR + DE, ragged lengths), configs[4] (8 concurrent streams: p50
   first-chunk latency) and the CPU fp32 oracle on one whole utterance (`cpu_baseline`).
 N > 1: configs[3] — 32 N utterances sharded over N ranks (one process per GPU): rank 0 broadcasts the shared prompt, scatters the
@@ -17,9 +17,11 @@ N > 1: configs[3] — 32 N utterances sharded over N ranks (one process per GPU)
   launcher as a child process before anything touches the GPU.  Weak scaling: per-GPU work (32 utterances) is fixed; the N = 1
   reference for it is the N = 1 line's `extra.batch32`.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel group, the LLM decode step (HBM-bound weight stream):
-algorithmic bytes per step / average step duration from HIP events recorded on the LLM's launch stream around every
-decode burst of the timed region.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`, ...);
+--dump-outputs DIR first writes the waveforms of the last timed step (see dump_outputs).  Everything else is measured with --full only:
+the live counter passes, `stages`, `extra`, `cpu_baseline`, `n1_reference` (N > 1) and `roofline`, which describes the dominant kernel
+group, the LLM decode step (HBM-bound weight stream): algorithmic bytes per step / average step duration from HIP events
+recorded on the LLM's launch stream around every decode burst of the timed region.
 """
 import argparse
 import json
@@ -42,6 +44,7 @@ PER_GPU = 32         # utterances per GPU in the sharded configuration (configs[
 HBM_PEAK_GBS = 8000.0
 MFMA_BF16_PEAK = 2500.0   # TFLOP/s dense
 FP32_MFMA_PEAK = 157.3
+DUMP_CAP_BYTES = 64_000_000   # --dump-outputs: at most 64 MB of arrays in all
 
 
 def llm_step_bytes(weight_bytes, kv_positions_sum, layers=24, n_kv=2, kv_elem_bytes=4):
@@ -453,9 +456,8 @@ def build_model(dev, max_batch):
 
 # ------------------------------------------------------------------------------------------------ N = 1
 def run_single(args):
-    # the live counter passes run first: child processes, done before this process initialises the GPU
-    live = live_counters() if (args.batch == 1 and not args.no_extra and 'RANK' not in os.environ) else {}
-    live_traffic = live.get('decode')
+    # --full: the live counter passes run first: child processes, done before this process initialises the GPU
+    live = live_counters() if (args.full and args.batch == 1 and not args.no_extra and 'RANK' not in os.environ) else {}
     import torch
     assert torch.cuda.is_available(), 'bench.py needs a GPU (the hot path has no CPU fallback)'
     dev_index = int(os.environ.get('CV2_BENCH_DEVICE', os.environ.get('LOCAL_RANK', 0)))
@@ -476,10 +478,13 @@ def run_single(args):
 
     B = args.batch
     model = build_model(dev, max(B, 1) if args.no_extra else 32)
-    st = StepTimer(model.llm)
-    flow_t, hift_t = StageTimer(model.flow, 'inference_batch'), StageTimer(model.hift_pool, 'inference_many')
-    if model.max_batch == 1:                  # serial scheduler path: HiFT runs inside _mel2wav (slice + vocoder), not through the pool
-        hift_t = StageTimer(model, '_mel2wav')
+    timers = ()
+    if args.full:                             # the roofline and stage split: events around the decode bursts and the flow / HiFT calls
+        st = StepTimer(model.llm)
+        flow_t, hift_t = StageTimer(model.flow, 'inference_batch'), StageTimer(model.hift_pool, 'inference_many')
+        if model.max_batch == 1:              # serial scheduler path: HiFT runs inside _mel2wav (slice + vocoder), not through the pool
+            hift_t = StageTimer(model, '_mel2wav')
+        timers = (st, flow_t, hift_t)
     if B == 1:
         reqs, forces = [request(1986, P_TOK, TEXT_LEN, dev)], [N_TOK]
     else:
@@ -491,18 +496,45 @@ def run_single(args):
     for _ in range(args.warmup):
         wavs, _ = run_calls(model, reqs, forces)
     barrier()
-    st.on = flow_t.on = hift_t.on = True
+    for t in timers:
+        t.on = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
         wavs, _ = run_calls(model, reqs, forces)          # yields CPU tensors: the device->host copy is inside the timed region
     barrier()
     dt = time.perf_counter() - t0
-    st.on = flow_t.on = hift_t.on = False
+    for t in timers:
+        t.on = False
     assert all(w.device.type == 'cpu' and torch.isfinite(w).all() for w in wavs)
     assert [w.shape[1] for w in wavs] == [960 * f for f in forces], 'forced-length run must produce 2 frames x 480 samples per token'
     audio_per_step = sum(w.shape[1] for w in wavs) / 24000.0
     value = audio_per_step * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wavs)
+    out = {
+        'metric': 'audio-sec/sec, CosyVoice2-0.5B-EU zero-shot FR', 'value': round(value, 3), 'unit': 'audio-s/s',
+        'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
+        'rtf': round(dt / (audio_per_step * args.steps), 5),
+        'config': {'workload': f'configs[{1 if B == 1 else 2}]: zero-shot FR{"+DE" if B > 1 else ""}, batch={B}, non-streaming, through CosyVoice2Model.tts() '
+                               f'(scheduler + D2H of the waveform inside the timed region), P=255{"/310" if B > 1 else ""} prompt tokens, '
+                               f'{TEXT_LEN} text tokens, {"250" if B == 1 else "U{150..500}"} generated tokens (forced), 10 Euler steps + CFG, RAS sampler; '
+                               f'LLM bf16 weights / fp32 KV, flow bf16 MFMA, HiFT fp32 data with two-plane bf16 MFMA products (three per term, ~2^-15; CV2_HIFT_PLANES=3: six, fp32-equivalent) and fp32 MFMA for the f0 predictor', 'batch_per_gpu': B,
+                   'audio_s_per_step_per_gpu': round(audio_per_step, 3)},
+    }
+    if args.full:
+        out.update(full_fields(args, model, timers, reqs, forces, dt, audio_per_step, live, dev))
+    print(json.dumps(out), flush=True)
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
 
+
+def full_fields(args, model, timers, reqs, forces, dt, audio_per_step, live, dev):
+    """--full: the roofline of the decode step and the stage split of the timed steps, then configs[2] / configs[4] and the CPU baseline."""
+    st, flow_t, hift_t = timers
+    B = args.batch
+    live_traffic = live.get('decode')
     dec_ms, dec_steps = st.result()
     kv_mean, n_steps = kv_positions_mean([lm_rows(r) for r in reqs], forces)
     assert dec_steps == n_steps * args.steps, (dec_steps, n_steps, args.steps)
@@ -518,15 +550,6 @@ def run_single(args):
         traffic, traffic_src = live_traffic if live_traffic is not None else pmc_decode_traffic(model.llm.decode_kernel_desc(B))
     pmc_flow, pmc_hift = pmc_stage_file('flow'), pmc_stage_file('hift')
     out = {
-        'metric': 'audio-sec/sec, CosyVoice2-0.5B-EU zero-shot FR', 'value': round(value, 3), 'unit': 'audio-s/s',
-        'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
-        'rtf': round(dt / (audio_per_step * args.steps), 5),
-        'config': {'workload': f'configs[{1 if B == 1 else 2}]: zero-shot FR{"+DE" if B > 1 else ""}, batch={B}, non-streaming, through CosyVoice2Model.tts() '
-                               f'(scheduler + D2H of the waveform inside the timed region), P=255{"/310" if B > 1 else ""} prompt tokens, '
-                               f'{TEXT_LEN} text tokens, {"250" if B == 1 else "U{150..500}"} generated tokens (forced), 10 Euler steps + CFG, RAS sampler; '
-                               f'LLM bf16 weights / fp32 KV, flow bf16 MFMA, HiFT fp32 data with two-plane bf16 MFMA products (three per term, ~2^-15; CV2_HIFT_PLANES=3: six, fp32-equivalent) and fp32 MFMA for the f0 predictor', 'batch_per_gpu': B,
-                   'audio_s_per_step_per_gpu': round(audio_per_step, 3)},
         'roofline': {'bound': 'hbm', 'kernel': model.llm.decode_kernel_desc(B),
                      'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4),
                      'traffic': traffic, 'traffic_source': traffic_src, 'bytes_per_launch': int(step_bytes), 'avg_launch_us': round(step_us, 2),
@@ -553,10 +576,23 @@ def run_single(args):
         out['extra'] = extras(model, st, flow_t, hift_t, dev)
     if not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(host_cores())
-    print(json.dumps(out), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return out
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: what the timed path returned in its last step (the waveforms its callers receive) as <path>/tts_speech_<i>.npy,
+    float32.  Above DUMP_CAP_BYTES in all, every array keeps the same seeded sample of its elements, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = [t.detach().cpu().float().numpy() for t in tensors]
+    total = sum(a.nbytes for a in arrs)
+    cap = DUMP_CAP_BYTES - 256 * len(arrs)                 # room for the .npy headers
+    for i, a in enumerate(arrs):
+        if total > cap:
+            flat = a.reshape(-1)
+            n = max(1, int(flat.size * cap / total))
+            a = flat[np.sort(np.random.default_rng(1986 + i).choice(flat.size, n, replace=False))]
+        np.save(os.path.join(path, f'tts_speech_{i}.npy'), a)
 
 
 def extras(model, st, flow_t, hift_t, dev):
@@ -788,7 +824,7 @@ def run_sharded(args):
     model = None if fake else build_model(dev, per)
     if model is not None:
         model.coalesce_ms = 50.0
-    st = StepTimer(model.llm) if model is not None else None
+    st = StepTimer(model.llm) if (model is not None and args.full) else None
 
     work = {'s': 0.0, 'utts': 0, 'audio_s': 0.0}          # this rank's own synthesis time inside the timed steps (collectives excluded)
 
@@ -835,6 +871,8 @@ def run_sharded(args):
     dt = max(r['wall_s'] for r in per_rank)
     if rank == 0:
         assert len(waves) == n_utts and all(w.numel() == 960 * 5 * x.numel() for w, x in zip(waves, texts)), 'gather returned the wrong waveforms'
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, waves)
         audio_per_step = sum(w.numel() for w in waves) / 24000.0
         out = {'metric': 'audio-sec/sec, CosyVoice2-0.5B-EU zero-shot FR', 'value': round(audio_per_step * args.steps / dt, 3), 'unit': 'audio-s/s',
                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
@@ -844,15 +882,16 @@ def run_sharded(args):
                'backend': (f'nccl = RCCL {".".join(map(str, torch.cuda.nccl.version()))} over xGMI' if backend == 'nccl' and not fake else backend),
                'per_rank': per_rank,
                'imbalance': round(max(r['work_s'] for r in per_rank) / max(min(r['work_s'] for r in per_rank), 1e-9), 3),
-               # the one-GPU reference measured INSIDE this run: what each rank's own shard (its utterances, no collectives) ran at; the
-               # committed N = 1 line's extra.batch32.value (the same 32-utterance workload through the same path) is quoted beside it
-               'n1_reference': n1_reference(per_rank, args.steps),
                'config': {'workload': f'configs[3]: {n_utts} utterances sharded over {world} ranks ({per} per GPU, length-balanced), zero-shot FR, P=255, texts of '
                                       f'30..100 tokens, 5 x text length forced speech tokens (150..500), non-streaming; broadcast prompt / scatter text ids / '
                                       f'gather waveforms over {"RCCL" if backend == "nccl" else backend} inside the timed region; every rank runs its shard as '
                                       f'one coalesced batch through CosyVoice2Model.tts()', 'batch_per_gpu': per,
                           'audio_s_per_step_total': round(audio_per_step, 2),
                           'scaling_reference': f"per-GPU work is fixed at {per} utterances: compare with N x the N=1 line's extra.batch32.value (32 per GPU there)"}}
+        if args.full:
+            # the one-GPU reference measured INSIDE this run: what each rank's own shard (its utterances, no collectives) ran at; the
+            # committed N = 1 line's extra.batch32.value (the same 32-utterance workload through the same path) is quoted beside it
+            out['n1_reference'] = n1_reference(per_rank, args.steps)
         if st is not None:
             sync()
             dec_ms, dec_steps = st.result()
@@ -888,8 +927,11 @@ def main():
     ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=None)
     ap.add_argument('--batch', type=int, default=1, help='N=1 only: utterances per step (1 = configs[1], 32 = configs[2])')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='N=1: skip the configs[2] / configs[4] measurements')
+    ap.add_argument('--full', action='store_true', help='also measure everything beside the headline: live counter passes, roofline and stage '
+                                                        'split, configs[2] / configs[4] (N=1), the CPU baseline, the one-GPU reference (N>1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the waveforms of the last timed step as DIR/tts_speech_<i>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='N=1: size the model for --batch only; with --full, skip the configs[2] / configs[4] measurements')
     ap.add_argument('--fresh-threads', action='store_true', help='concurrent calls from new threads per round instead of persistent workers (CallerPool)')
     args = ap.parse_args()
     CallerPool.fresh = bool(args.fresh_threads)
@@ -901,6 +943,8 @@ def main():
         args.steps = 6 if (args.gpus == 1 and not force_sharded) else 2
     if args.warmup is None:
         args.warmup = 2 if (args.gpus == 1 and not force_sharded) else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if (args.gpus > 1 or force_sharded) and 'RANK' not in os.environ:
         # started without a launcher: spawn one rank per GPU as CHILD processes before anything in this process touches the GPU
         # (a process that has initialised the GPU must never exec another program on this pool)

@@ -294,7 +294,7 @@ def test_bench_gpus2_spawns_ranks_and_gathers(tmp_path):
     env = dict(os.environ, CV2_BENCH_BACKEND='gloo', CV2_BENCH_FAKE_SYNTH='1', CV2_BENCH_PER_GPU='5', MASTER_PORT=str(_free_port()))
     env.pop('RANK', None)
     env.pop('WORLD_SIZE', None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1'], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full'], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -493,6 +493,25 @@ def test_bistream_host_bookkeeping_matches_the_oracle():
         assert got == want and eng.slots[2]['out'] == want_out, (seed, got[:8], want[:8])
         assert eng.feeds[-1][2] and sum(1 for f in eng.feeds if f[2]) == 1             # exactly one final feed, the last one
         assert pulled == sorted(pulled) and pulled[0] == 0                              # pieces are pulled lazily, never ahead of a feed they enable
+
+
+def test_bench_dump_outputs_keeps_or_samples_under_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float32 waveforms as tts_speech_<i>.npy, whole when they fit the cap; above it every array
+    keeps the same seeded sample of its elements from run to run, and the files stay under the cap."""
+    import bench
+    wavs = [torch.randn(1, 960 * n, generator=torch.Generator().manual_seed(n)) for n in (3, 5)]
+    bench.dump_outputs(str(tmp_path / 'whole'), wavs)
+    for i, w in enumerate(wavs):
+        a = np.load(tmp_path / 'whole' / f'tts_speech_{i}.npy')
+        assert a.dtype == np.float32 and np.array_equal(a, w.numpy())
+    monkeypatch.setattr(bench, 'DUMP_CAP_BYTES', 8192)
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), wavs)
+    files = sorted((tmp_path / 's1').iterdir())
+    assert [f.name for f in files] == ['tts_speech_0.npy', 'tts_speech_1.npy'] and sum(f.stat().st_size for f in files) <= 8192
+    for i, w in enumerate(wavs):
+        a, b = np.load(tmp_path / 's1' / f'tts_speech_{i}.npy'), np.load(tmp_path / 's2' / f'tts_speech_{i}.npy')
+        assert a.dtype == np.float32 and 0 < a.size < w.numel() and np.array_equal(a, b) and np.isin(a, w.numpy()).all()
 
 
 def test_bench_caller_pool_runs_every_call_once_in_both_modes():

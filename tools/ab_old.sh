@@ -4,6 +4,6 @@
 cd "$(dirname "$0")/.."
 for rep in 1 2; do
 for d in _ab_old .; do
-  (cd $d && python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$d', d['value'], d['stages']['ms_per_step'])")
+  (cd $d && python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$d', d['value'], d['stages']['ms_per_step'])")
 done
 done

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for v in 0 1; do
   echo "CV2_HIFT_FP32=$v"
-  CV2_HIFT_FP32=$v python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+  CV2_HIFT_FP32=$v python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(' B=1', d['value'], d['stages']['ms_per_step'])
