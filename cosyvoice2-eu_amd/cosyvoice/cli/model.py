@@ -25,6 +25,7 @@ What is different, by design:
         all of them, the flow runs over the packed ragged batch, HiFT on a pool of streams);
       - the two kinds exclude each other (a batch uses slots 0..n-1): streams hold the model in shared mode, a batch in exclusive mode.
 """
+import logging
 import os
 import threading
 import time
@@ -71,7 +72,12 @@ class CosyVoice2Model:
         self.device = torch.device(device or 'cuda')
         if self.device.index is None:                  # set_device needs an index (threads started later switch to this device)
             self.device = torch.device('cuda', torch.cuda.current_device())
-        self.fp16 = fp16                       # accepted for signature compatibility; the HIP path fixes its own dtypes
+        # fp16 (the reference halves the LLM and the flow, model.py:35-43, and runs flow.inference under autocast): here the flow stage runs
+        # on fp16 matrix-core operands -- weights, GEMM / convolution activations, attention q / k / v and probabilities, the stream caches --
+        # rounded to nearest even and saturated to +-65504, with fp32 accumulation, norms, softmax statistics, residual stream and Euler state
+        # (FlowEngine(operands='fp16')).  The LLM stays bf16 (bit-exact against the reference on bf16-rounded weights) and HiFT fp32, as
+        # HiFT stays fp32 in the reference.
+        self.fp16 = fp16
         from cv2amd.config import Config
         self.config = config or Config()       # hyper-parameters of cosyvoice2.yaml (the reference receives built modules instead)
         self.min_token_text_ratio, self.max_token_text_ratio = 2, 20    # defaults of Qwen2LM.inference (llm.py:586-587)
@@ -190,8 +196,14 @@ class CosyVoice2Model:
         cfg = self.config
         self.llm = LLMEngine(llm_sd, self.device, max_seqs=B, max_pos=max_text + max_prompt + max_new + 8, max_out=max_new,
                              sampling=cfg.sampling)
+        if self.fp16:
+            from cv2amd import checkpoint
+            r = checkpoint.fp16_range(flow_sd)
+            if r['n_over'] or r['n_flush']:
+                logging.warning('fp16=True: %d flow weights exceed 65504 (saturated; largest |w| %.4g in %s), %d nonzero ones are below 2^-24 '
+                                '(flushed to zero)', r['n_over'], r['max_abs'], r['max_key'], r['n_flush'])
         self.flow = FlowEngine(flow_sd, self.device, max_utts=B, max_len=2 * (max_prompt + max_new), n_timesteps=cfg.n_timesteps,
-                               cfg_rate=cfg.inference_cfg_rate)
+                               cfg_rate=cfg.inference_cfg_rate, operands='fp16' if self.fp16 else 'bf16')
         self.flow.pre_lookahead_len, self.flow.token_mel_ratio, self.flow.input_frame_rate = cfg.pre_lookahead_len, cfg.token_mel_ratio, cfg.input_frame_rate
         self.hift_pool = HiftPool(hift_sd, self.device, max_frames=2 * max_new + self.mel_cache_len, n=min(4, B), batch_lanes=0 if os.environ.get('CV2_HIFT_BATCH') == '0' else min(8, B))      # (CV2_HIFT_BATCH=0: A/B switch, one vocoder call per chunk)
         self.hift = self.hift_pool.engines[0]

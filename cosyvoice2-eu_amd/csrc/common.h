@@ -39,6 +39,49 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
 __device__ __forceinline__ float bf2f(uint16_t h) {
     return __builtin_bit_cast(float, ((uint32_t)h) << 16);
 }
+// ---- 16-bit matrix-operand formats of the flow engine (cv2_flow_dims.operands): one trait per format, one kernel body per use ----
+// v8: the 8-element MFMA operand fragment; from_f32 / pack2 / cvt8: fp32 -> 16-bit; to_f32: back; mfma16 / mfma32: the 16x16x32 and
+// 32x32x16 products with fp32 accumulation.  OpBF16 reproduces the conversions the bf16 code used before the trait existed, site for
+// site: from_f32 is f2bf (integer RNE), pack2 / cvt8 are v_cvt_pk_bf16_f32 (RNE).
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(8))) float f32x8;
+struct OpBF16 {
+    typedef bf16x8 v8;
+    static __device__ __forceinline__ uint16_t from_f32(float f) { return f2bf(f); }
+    static __device__ __forceinline__ float to_f32(uint16_t h) { return bf2f(h); }
+    static __device__ __forceinline__ uint32_t pack2(float a, float b) {
+        typedef __attribute__((ext_vector_type(2))) float f32x2;
+        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){a, b}, bf16x2));
+    }
+    static __device__ __forceinline__ v8 cvt8(f32x8 v) { return __builtin_convertvector(v, bf16x8); }
+    static __device__ __forceinline__ f32x4 mfma16(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ f32x16 mfma32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+// fp16: round to nearest even, saturating to +-65504 (an overflowing activation stays finite and large instead of becoming inf); subnormals
+// kept, as torch's .half() keeps them.  The clamp + (_Float16) conversion compiles to v_med3_f32 + v_cvt_pk_f16_f32 (RNE) on gfx950; the
+// truncating v_cvt_pkrtz_f16_f32 would bias every product and is not used.
+struct OpF16 {
+    typedef f16x8 v8;
+    static __device__ __forceinline__ float sat(float f) { return __builtin_amdgcn_fmed3f(f, -65504.f, 65504.f); }
+    static __device__ __forceinline__ uint16_t from_f32(float f) { return __builtin_bit_cast(uint16_t, (_Float16)sat(f)); }
+    static __device__ __forceinline__ float to_f32(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+    static __device__ __forceinline__ uint32_t pack2(float a, float b) {
+        typedef __attribute__((ext_vector_type(2))) float f32x2;
+        typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){sat(a), sat(b)}, f16x2));
+    }
+    static __device__ __forceinline__ v8 cvt8(f32x8 v) {
+        f32x8 s;
+#pragma unroll
+        for (int i = 0; i < 8; i++) s[i] = sat(v[i]);
+        return __builtin_convertvector(s, f16x8);
+    }
+    static __device__ __forceinline__ f32x4 mfma16(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ f32x16 mfma32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+template <class OP> using v8_t = typename OP::v8;
+
 // x = hi + lo with hi, lo bf16: ~16 mantissa bits of x survive two bf16 MFMAs
 __device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) {
     hi = f2bf(x);

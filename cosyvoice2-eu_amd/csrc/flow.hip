@@ -14,6 +14,8 @@
 //   k_attn_est_dma         MFMA bf16   the same from 4 096 rows on, key / value tiles by LDS DMA (three stages, three waves per SIMD)
 //   k_relsoftmax           HBM         conformer rel-pos softmax over explicit score matrices (encoder only, ~2 % of FLOPs)
 //   k_layernorm, k_pack, k_euler, ...  HBM   small row-wise kernels
+// Every kernel that reads or writes a 16-bit matrix operand takes its format as a trait (OP: OpBF16 / OpF16, common.h), fixed per engine by
+// cv2_flow_dims.operands; "bf16" in the comments below stands for that format.
 #include "gemm_launch.h"
 #include "skinny_launch.h"
 #include "../../include/cv2_amd.h"
@@ -32,6 +34,14 @@ extern "C" int cv2_gemm_bf16(const uint16_t* a, int64_t lda, const uint16_t* w, 
     g.bias = bias; g.out_f32 = out; g.ldo = ldo;
     return gemm_launch_cfg(g, n % 256 == 0 && n <= 256 ? 1 : 0, 1, true, (hipStream_t)stream);
 }
+// the same product on fp16 operands (a and w_packed hold fp16 bit patterns): the GEMM instantiations of an fp16 flow engine
+extern "C" int cv2_gemm_f16(const uint16_t* a, int64_t lda, const uint16_t* w, const float* bias, float* out, int64_t ldo,
+                            int32_t m, int32_t n, int32_t k, void* stream) {
+    CV2_CHECK(a && w && out, "cv2_gemm_f16: null argument");
+    GemmArgs g = gemm_args(a, lda, 0, w, m, n, k);
+    g.bias = bias; g.out_f32 = out; g.ldo = ldo;
+    return gemm_launch_cfg<OpF16>(g, n % 256 == 0 && n <= 256 ? 1 : 0, 1, true, (hipStream_t)stream);
+}
 
 // =========================================================================== small kernels
 struct LnArgs {
@@ -41,7 +51,7 @@ struct LnArgs {
     float* out_f32; long ldo; uint16_t* out_bf16; long ldo16;
 };
 // one wave per row; C in {256, 512}
-template <int PER>
+template <int PER, class OP>
 __global__ __launch_bounds__(256) void k_layernorm(LnArgs a) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= a.rows) return;
@@ -68,11 +78,12 @@ __global__ __launch_bounds__(256) void k_layernorm(LnArgs a) {
     if (a.out_f32) for (int i = 0; i < per; i += 4)
         *reinterpret_cast<f32x4*>(a.out_f32 + (size_t)row * a.ldo + lane * per + i) = (f32x4){v[i], v[i + 1], v[i + 2], v[i + 3]};
     if (a.out_bf16) for (int i = 0; i < per; i += 4)
-        *reinterpret_cast<uint2*>(a.out_bf16 + (size_t)row * a.ldo16 + lane * per + i) = make_uint2(pack_bf16x2(v[i], v[i + 1]), pack_bf16x2(v[i + 2], v[i + 3]));
+        *reinterpret_cast<uint2*>(a.out_bf16 + (size_t)row * a.ldo16 + lane * per + i) = make_uint2(OP::pack2(v[i], v[i + 1]), OP::pack2(v[i + 2], v[i + 3]));
 }
 
 // token ids -> embedding rows (flow.py:252-256): bf16 [rows][512]; ids clamped at 0; rows beyond the sequence -> 0
 struct EmbedPtrArgs { const int* const* tokens; const float* table; SeqTable seq; int rows; uint16_t* out; };
+template <class OP>
 __global__ __launch_bounds__(256) void k_embed_tokens_ptr(EmbedPtrArgs a) {
     const int row = blockIdx.x * 2 + (threadIdx.x >> 7), c = (threadIdx.x & 127) * 4;
     if (row >= a.rows) return;
@@ -86,16 +97,18 @@ __global__ __launch_bounds__(256) void k_embed_tokens_ptr(EmbedPtrArgs a) {
             v = *reinterpret_cast<const f32x4*>(a.table + (size_t)id * 512 + c);
         }
     }
-    *reinterpret_cast<uint2*>(a.out + (size_t)row * 512 + c) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    *reinterpret_cast<uint2*>(a.out + (size_t)row * 512 + c) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
 }
 // 3 look-ahead context rows (fp32 [3][512]) -> bf16 rows
+template <class OP>
 __global__ __launch_bounds__(256) void k_ctx_rows(const float* ctx, uint16_t* out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 3 * 512) out[i] = f2bf(ctx[i]);
+    if (i < 3 * 512) out[i] = OP::from_f32(ctx[i]);
 }
 
 // fp32 [rows][512] -> bf16 (plain cast with mask), used for externally supplied encoder inputs
 struct CastArgs { const float* x; uint16_t* out; SeqTable seq; int rows; int C; const int* src_row_off; };
+template <class OP>
 __global__ __launch_bounds__(256) void k_cast_rows(CastArgs a) {
     const int per_row = a.C / 4;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -107,11 +120,12 @@ __global__ __launch_bounds__(256) void k_cast_rows(CastArgs a) {
         const int t = row - a.seq.seq_start[s];
         if (t < a.seq.seq_len[s]) v = *reinterpret_cast<const f32x4*>(a.x + ((size_t)a.src_row_off[s] + t) * a.C + c);
     }
-    *reinterpret_cast<uint2*>(a.out + (size_t)row * a.C + c) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    *reinterpret_cast<uint2*>(a.out + (size_t)row * a.C + c) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
 }
 
 // Upsample1D nearest x2 (upsample_encoder.py:55-57): token-rate fp32 rows -> mel-rate bf16 rows of the new layout
 struct RepeatArgs { const float* x; SeqTable seq_in; SeqTable seq_out; int rows_out; uint16_t* out; };
+template <class OP>
 __global__ __launch_bounds__(256) void k_repeat2(RepeatArgs a) {
     const int row = blockIdx.x * 2 + (threadIdx.x >> 7), c = (threadIdx.x & 127) * 4;
     if (row >= a.rows_out) return;
@@ -121,10 +135,11 @@ __global__ __launch_bounds__(256) void k_repeat2(RepeatArgs a) {
         const int t = row - a.seq_out.seq_start[s];
         if (t < a.seq_out.seq_len[s]) v = *reinterpret_cast<const f32x4*>(a.x + ((size_t)a.seq_in.seq_start[s] + (t >> 1)) * 512 + c);
     }
-    *reinterpret_cast<uint2*>(a.out + (size_t)row * 512 + c) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    *reinterpret_cast<uint2*>(a.out + (size_t)row * 512 + c) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
 }
 
 // EspnetRelPositionalEncoding (embedding.py:226-302): rows r = 0 .. 2T-2 hold position T-1-r; even cols sin, odd cos.
+template <class OP>
 __global__ __launch_bounds__(256) void k_pos_emb(uint16_t* out, int T, int rows_pad) {
     const int r = blockIdx.x, i2 = threadIdx.x;              // 256 (sin, cos) pairs
     float sv = 0.f, cv = 0.f;
@@ -133,12 +148,13 @@ __global__ __launch_bounds__(256) void k_pos_emb(uint16_t* out, int T, int rows_
         const float div = expf((float)(2 * i2) * (-(logf(10000.0f) / 512.f)));
         sv = sinf(pos * div); cv = cosf(pos * div);
     }
-    if (r < rows_pad) *reinterpret_cast<uint32_t*>(out + (size_t)r * 512 + 2 * i2) = pack_bf16x2(sv, cv);
+    if (r < rows_pad) *reinterpret_cast<uint32_t*>(out + (size_t)r * 512 + 2 * i2) = OP::pack2(sv, cv);
 }
 
 // softmax over (ac[i][j] + bd[i][T-1-ig+j]) / 8 with the chunk mask (attention.py:225-247 rel_shift, :297-330); the launch's query rows
 // i < n_new are positions ig = n0 + i of a sequence of T keys (n0 = 0, n_new = T: the whole sequence; cached streaming: the new rows)
 struct RelSmArgs { const float* ac; const float* bd; uint16_t* probs; int T, Mp, Tk, P, chunk, n0, n_new; };
+template <class OP>
 __global__ __launch_bounds__(256) void k_relsoftmax(RelSmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sc = reinterpret_cast<float*>(smem);
@@ -162,7 +178,7 @@ __global__ __launch_bounds__(256) void k_relsoftmax(RelSmArgs a) {
     if ((tid & 63) == 0) red[4 + (tid >> 6)] = sum;
     __syncthreads();
     const float inv = 1.f / (red[4] + red[5] + red[6] + red[7]);
-    for (int j = tid; j < a.Tk; j += 256) pr[j] = j < kmax ? f2bf(sc[j] * inv) : (uint16_t)0;
+    for (int j = tid; j < a.Tk; j += 256) pr[j] = j < kmax ? OP::from_f32(sc[j] * inv) : (uint16_t)0;
 }
 
 // F.normalize(embedding) -> Linear 192 -> 80 (flow.py:248-249), fp32; one block per utterance
@@ -203,6 +219,7 @@ struct PackArgs {
     // below `lead` belong to no sequence (their twin rows do not exist).
     const int* pos0; const int* mu_start; int twin, lead;
 };
+template <class OP>
 __global__ __launch_bounds__(256) void k_euler_pack(PackArgs a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const int row = idx / 20, c = (idx % 20) * 4;            // 80 channels = 20 float4
@@ -229,7 +246,7 @@ __global__ __launch_bounds__(256) void k_euler_pack(PackArgs a) {
         }
     }
     *reinterpret_cast<f32x4*>(a.x + (size_t)row * 80 + c) = x;
-    const uint2 xb = make_uint2(pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]));
+    const uint2 xb = make_uint2(OP::pack2(x[0], x[1]), OP::pack2(x[2], x[3]));
     uint16_t* r0 = a.a0 + (size_t)row * 320 + c;
     uint16_t* r1 = a.a0 + (size_t)(row + a.twin) * 320 + c;
     if (row < a.lead) {                                              // lead rows: no twin
@@ -238,9 +255,9 @@ __global__ __launch_bounds__(256) void k_euler_pack(PackArgs a) {
         return;
     }
     *reinterpret_cast<uint2*>(r0) = xb;
-    *reinterpret_cast<uint2*>(r0 + 80) = make_uint2(pack_bf16x2(mu[0], mu[1]), pack_bf16x2(mu[2], mu[3]));
-    *reinterpret_cast<uint2*>(r0 + 160) = make_uint2(pack_bf16x2(sp[0], sp[1]), pack_bf16x2(sp[2], sp[3]));
-    *reinterpret_cast<uint2*>(r0 + 240) = make_uint2(pack_bf16x2(cd[0], cd[1]), pack_bf16x2(cd[2], cd[3]));
+    *reinterpret_cast<uint2*>(r0 + 80) = make_uint2(OP::pack2(mu[0], mu[1]), OP::pack2(mu[2], mu[3]));
+    *reinterpret_cast<uint2*>(r0 + 160) = make_uint2(OP::pack2(sp[0], sp[1]), OP::pack2(sp[2], sp[3]));
+    *reinterpret_cast<uint2*>(r0 + 240) = make_uint2(OP::pack2(cd[0], cd[1]), OP::pack2(cd[2], cd[3]));
     *reinterpret_cast<uint2*>(r1) = xb;
     *reinterpret_cast<uint2*>(r1 + 80) = make_uint2(0u, 0u);
     *reinterpret_cast<uint2*>(r1 + 160) = make_uint2(0u, 0u);
@@ -294,6 +311,7 @@ __global__ __launch_bounds__(256) void k_conv_tail(ConvTailArgs a) {
 
 // TensorRT-seam pack / unpack (flow_matching.py:125-150): channel-major (2,80,T) tensors <-> packed rows
 struct SeamPackArgs { const float* x; const float* mu; const float* spks; const float* cond; int T; int row1; uint16_t* a0; int rows; };
+template <class OP>
 __global__ __launch_bounds__(256) void k_seam_pack(SeamPackArgs a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const int row = idx / 320, c = idx % 320;
@@ -305,7 +323,7 @@ __global__ __launch_bounds__(256) void k_seam_pack(SeamPackArgs a) {
         const size_t o = ((size_t)b * 80 + ch) * a.T + t;
         v = g == 0 ? a.x[o] : g == 1 ? a.mu[o] : g == 2 ? a.spks[b * 80 + ch] : a.cond[o];
     }
-    a.a0[(size_t)row * 320 + c] = f2bf(v);
+    a.a0[(size_t)row * 320 + c] = OP::from_f32(v);
 }
 __global__ __launch_bounds__(256) void k_seam_unpack(const float* v, float* x, int T, int row1) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -354,8 +372,8 @@ struct AttnEstArgs {
 // matrix-core k group: the two forms agree to fp32 round-off, not bit for bit.
 __device__ __forceinline__ int att_kswz(int i) { return (i >> 2) * 2 + ((i >> 1) & 1); }      // i = score row (0 .. 15): two rows per value
 // S^T: 4 key tiles x (d = 64 in two k-steps), K fragments shared by the QS query sub-tiles
-template <int QS, bool SWZ>
-__device__ __forceinline__ void att_qk(const uint16_t* Kt, const bf16x8 (&qf)[QS][2], f32x4 (&sacc)[QS][4], int q16, int g) {
+template <class OP, int QS, bool SWZ>
+__device__ __forceinline__ void att_qk(const uint16_t* Kt, const v8_t<OP> (&qf)[QS][2], f32x4 (&sacc)[QS][4], int q16, int g) {
 #pragma unroll
     for (int k4 = 0; k4 < 4; k4++) {
 #pragma unroll
@@ -363,12 +381,12 @@ __device__ __forceinline__ void att_qk(const uint16_t* Kt, const bf16x8 (&qf)[QS
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) {
             // SWZ: score row i = q16 of key tile k4 is key 32 (k4 / 2) + 8 (i / 4) + 4 (k4 % 2) + i % 4 (see the V^T read in att_pv)
-            const bf16x8 kf = SWZ ? *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(Kt) + (k4 >> 1) * 4096 + (k4 & 1) * 512 +
+            const v8_t<OP> kf = SWZ ? *reinterpret_cast<const v8_t<OP>*>(reinterpret_cast<const char*>(Kt) + (k4 >> 1) * 4096 + (k4 & 1) * 512 +
                                                                      (((8 * (q16 >> 2) + (q16 & 3)) * 128 + ((g ^ att_kswz(q16)) << 4)) ^ (ks << 6)))
-                                  : *reinterpret_cast<const bf16x8*>(&Kt[(16 * k4 + q16) * AK_LD + ks * 32 + g * 8]);
+                                  : *reinterpret_cast<const v8_t<OP>*>(&Kt[(16 * k4 + q16) * AK_LD + ks * 32 + g * 8]);
 #pragma unroll
             for (int u = 0; u < QS; u++) {
-                sacc[u][k4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[u][ks], sacc[u][k4], 0, 0, 0);
+                sacc[u][k4] = OP::mfma16(kf, qf[u][ks], sacc[u][k4]);
             }
         }
     }
@@ -376,8 +394,8 @@ __device__ __forceinline__ void att_qk(const uint16_t* Kt, const bf16x8 (&qf)[QS
 // softmax in the exp2 domain on the RAW scores: p = 2^(s C - m C), C = log2(e) / sqrt(64), one FMA + one v_exp_f32 per score.
 // Masking and the rescale of O are wave-uniform branches: only the last tile(s) of a sequence mask, and the running maximum
 // stops moving after the first few tiles.
-template <int QS, bool SWZ>
-__device__ __forceinline__ void att_softmax(f32x4 (&sacc)[QS][4], bf16x8 (&pf)[QS][2], f32x4 (&o)[QS][4], float (&mrun)[QS], float (&lrun)[QS],
+template <class OP, int QS, bool SWZ>
+__device__ __forceinline__ void att_softmax(f32x4 (&sacc)[QS][4], v8_t<OP> (&pf)[QS][2], f32x4 (&o)[QS][4], float (&mrun)[QS], float (&lrun)[QS],
                                             const int (&kmax_q)[QS], int kt, int g) {
     constexpr float SC = 0.125f * 1.4426950408889634f;
 #pragma unroll
@@ -419,50 +437,49 @@ __device__ __forceinline__ void att_softmax(f32x4 (&sacc)[QS][4], bf16x8 (&pf)[Q
         }
 #pragma unroll
         for (int kp = 0; kp < 2; kp++) {
-            typedef __attribute__((ext_vector_type(8))) float f32x8;
-            const f32x8 pv = {sacc[u][2 * kp][0], sacc[u][2 * kp][1], sacc[u][2 * kp][2], sacc[u][2 * kp][3],
+                        const f32x8 pv = {sacc[u][2 * kp][0], sacc[u][2 * kp][1], sacc[u][2 * kp][2], sacc[u][2 * kp][3],
                               sacc[u][2 * kp + 1][0], sacc[u][2 * kp + 1][1], sacc[u][2 * kp + 1][2], sacc[u][2 * kp + 1][3]};
-            pf[u][kp] = __builtin_convertvector(pv, bf16x8);
+            pf[u][kp] = OP::cvt8(pv);
         }
     }
 }
 // O^T += V^T P^T ; k slots of key-pair tile kp: j < 4 -> key 32kp + 4g + j, j >= 4 -> key 32kp + 16 + 4g + (j - 4)
-template <int QS, bool SWZ>
-__device__ __forceinline__ void att_pv(const uint16_t* Vt, const bf16x8 (&pf)[QS][2], f32x4 (&o)[QS][4], int q16, int g) {
+template <class OP, int QS, bool SWZ>
+__device__ __forceinline__ void att_pv(const uint16_t* Vt, const v8_t<OP> (&pf)[QS][2], f32x4 (&o)[QS][4], int q16, int g) {
 #pragma unroll
     for (int kp = 0; kp < 2; kp++)
 #pragma unroll
         for (int dt = 0; dt < 4; dt++) {
-            bf16x8 vf;
+            v8_t<OP> vf;
             if (SWZ) {                       // the lane's eight P entries of key-pair tile kp are the CONSECUTIVE keys 32 kp + 8 g .. + 7: one 16-byte chunk
-                vf = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(Vt) + dt * 2048 + ((q16 * 128 + ((g ^ (q16 & 7)) << 4)) ^ (kp << 6)));
+                vf = *reinterpret_cast<const v8_t<OP>*>(reinterpret_cast<const char*>(Vt) + dt * 2048 + ((q16 * 128 + ((g ^ (q16 & 7)) << 4)) ^ (kp << 6)));
             } else {
                 const uint16_t* vrow = &Vt[(16 * dt + q16) * AV_LD + 32 * kp + 4 * g];
                 const uint2 lo = *reinterpret_cast<const uint2*>(vrow);
                 const uint2 hi = *reinterpret_cast<const uint2*>(vrow + 16);
-                vf = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+                vf = __builtin_bit_cast(v8_t<OP>, make_uint4(lo.x, lo.y, hi.x, hi.y));
             }
 #pragma unroll
             for (int u = 0; u < QS; u++) {
-                o[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[u][kp], o[u][dt], 0, 0, 0);
+                o[u][dt] = OP::mfma16(vf, pf[u][kp], o[u][dt]);
             }
         }
 }
-template <int QS, bool SWZ = false>
-__device__ __forceinline__ void att_est_tile(const uint16_t* Kt, const uint16_t* Vt, const bf16x8 (&qf)[QS][2], f32x4 (&o)[QS][4],
+template <class OP, int QS, bool SWZ = false>
+__device__ __forceinline__ void att_est_tile(const uint16_t* Kt, const uint16_t* Vt, const v8_t<OP> (&qf)[QS][2], f32x4 (&o)[QS][4],
                                              float (&mrun)[QS], float (&lrun)[QS], const int (&kmax_q)[QS], int kt, int q16, int g) {
     f32x4 sacc[QS][4];
-    bf16x8 pf[QS][2];
-    att_qk<QS, SWZ>(Kt, qf, sacc, q16, g);
-    att_softmax<QS, SWZ>(sacc, pf, o, mrun, lrun, kmax_q, kt, g);
-    att_pv<QS, SWZ>(Vt, pf, o, q16, g);
+    v8_t<OP> pf[QS][2];
+    att_qk<OP, QS, SWZ>(Kt, qf, sacc, q16, g);
+    att_softmax<OP, QS, SWZ>(sacc, pf, o, mrun, lrun, kmax_q, kt, g);
+    att_pv<OP, QS, SWZ>(Vt, pf, o, q16, g);
 }
 // QS query sub-tiles of 16 rows per wave, NW waves (block = 16*NW*QS rows): K / V^T fragments read from LDS once serve QS MFMAs;
 // NW = 2 doubles the block count for single-utterance calls, whose 64-row tiles would not even fill the chip once.
 // KSP = 2: a second group of NW waves works on the odd key tiles of the same queries (own LDS tiles, own register sets) and the two
 // (max, sum, O) states are merged through LDS at the end.  One utterance gives only one wave per SIMD otherwise, and every LDS /
 // MFMA / transcendental latency of the tile body is then exposed (phase stamps: ~1400 cycles of compute per 64-key tile).
-template <int QS, int NW, int KSP = 1, bool CACHE = false>
+template <class OP, int QS, int NW, int KSP = 1, bool CACHE = false>
 __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
     __shared__ __attribute__((aligned(16))) uint16_t Ks_[KSP][2][64 * AK_LD];
     __shared__ __attribute__((aligned(16))) uint16_t Vs_[KSP][2][64 * AV_LD];
@@ -519,12 +536,12 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
     const int kmax_blk = a.chunk > 0 ? min(klen, ((p0 + t0 + RB * QS - 1) / a.chunk + 1) * a.chunk) : klen;
     const int ntiles = (kmax_blk + 63) / 64;
 
-    bf16x8 qf[QS][2];
+    v8_t<OP> qf[QS][2];
 #pragma unroll
     for (int u = 0; u < QS; u++)
 #pragma unroll
         for (int ks = 0; ks < 2; ks++)
-            qf[u][ks] = *reinterpret_cast<const bf16x8*>(a.qk + (size_t)(m0 + RB * u + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
+            qf[u][ks] = *reinterpret_cast<const v8_t<OP>*>(a.qk + (size_t)(m0 + RB * u + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
 
     // staging: thread -> NCH K chunks (row, 16-B chunk) and NCH V^T chunks of the 64-key tile.  TWO register sets (A, B) keep the
     // next two tiles in flight: with one set the loop ran at the latency of a tile load (~3000 cycles per 64 keys at one
@@ -590,7 +607,7 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
             for (int u = 0; u < QS; u++) kmask_q[u] = kt < ntiles ? kmax_q[u] : 0;
             SK_ACC(2, ATT_LSTORE(A, 0) __syncthreads());             // [2] staging incl. the wait for the tile's loads
             ATT_GLOAD(A, min(kt + 2 * KSP, last))
-            SK_ACC(3, att_est_tile<QS>(Ks[0], Vs[0], qf, o, mrun, lrun, kmask_q, kt, q16, g));     // [3] tile compute
+            SK_ACC(3, (att_est_tile<OP, QS>(Ks[0], Vs[0], qf, o, mrun, lrun, kmask_q, kt, q16, g)));     // [3] tile compute
         }
         if (r + 1 >= rounds) break;
         {
@@ -599,7 +616,7 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
             for (int u = 0; u < QS; u++) kmask_q[u] = kt < ntiles ? kmax_q[u] : 0;
             SK_ACC(2, ATT_LSTORE(B, 1) __syncthreads());
             ATT_GLOAD(B, min(kt + 2 * KSP, last))
-            SK_ACC(3, att_est_tile<QS>(Ks[1], Vs[1], qf, o, mrun, lrun, kmask_q, kt, q16, g));
+            SK_ACC(3, (att_est_tile<OP, QS>(Ks[1], Vs[1], qf, o, mrun, lrun, kmask_q, kt, q16, g)));
         }
     }
     SK_STAMP(4);
@@ -649,7 +666,7 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
         const float inv = (tq[u] < len && l > 0.f) ? 1.f / l : 0.f;
 #pragma unroll
         for (int dt = 0; dt < 4; dt++)
-            *reinterpret_cast<uint2*>(orow[u] + 16 * dt) = make_uint2(pack_bf16x2(o[u][dt][0] * inv, o[u][dt][1] * inv), pack_bf16x2(o[u][dt][2] * inv, o[u][dt][3] * inv));
+            *reinterpret_cast<uint2*>(orow[u] + 16 * dt) = make_uint2(OP::pack2(o[u][dt][0] * inv, o[u][dt][1] * inv), OP::pack2(o[u][dt][2] * inv, o[u][dt][3] * inv));
     }
 #ifdef CV2_STAMPS
     SK_STAMP(5);
@@ -673,7 +690,7 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
 #ifndef ATT_STAGES
 #define ATT_STAGES 2     // LDS stages of the DMA attention: 2 = 32 KB per block, four blocks per CU (3: two tiles in flight, three blocks; A/B)
 #endif
-template <int QS, bool CACHE = false>
+template <class OP, int QS, bool CACHE = false>
 __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
     constexpr int NW = 4, RB = 16 * NW;
     __shared__ __attribute__((aligned(1024))) uint16_t Ks[ATT_STAGES][64 * 64];
@@ -760,12 +777,12 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
 #endif
     // q fragments: loaded AFTER the first DMAs and consumed (empty asm) before the loop, so that the compiler's own wait for these loads sits
     // here -- placed at their first use inside the loop it would be a vmcnt(0) in every iteration, i.e. a wait for the DMA just issued
-    bf16x8 qf[QS][2];
+    v8_t<OP> qf[QS][2];
 #pragma unroll
     for (int u = 0; u < QS; u++)
 #pragma unroll
         for (int ks = 0; ks < 2; ks++)
-            qf[u][ks] = *reinterpret_cast<const bf16x8*>(a.qk + (size_t)(m0 + RB * u + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
+            qf[u][ks] = *reinterpret_cast<const v8_t<OP>*>(a.qk + (size_t)(m0 + RB * u + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
 #pragma unroll
     for (int u = 0; u < QS; u++)
 #pragma unroll
@@ -778,7 +795,7 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         dma(min(kt + 1, last), st ^ 1);
-        att_est_tile<QS, true>(Ks[st], Vs[st], qf, o, mrun, lrun, kmax_q, kt, q16, g);
+        att_est_tile<OP, QS, true>(Ks[st], Vs[st], qf, o, mrun, lrun, kmax_q, kt, q16, g);
         st ^= 1;
     }
 #else
@@ -793,7 +810,7 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
         SK_TICK(tc_);
         dma(min(kt + 2, last), st >= 1 ? st - 1 : 2);
         SK_TICK(td_);
-        att_est_tile<QS, true>(Ks[st], Vs[st], qf, o, mrun, lrun, kmax_q, kt, q16, g);
+        att_est_tile<OP, QS, true>(Ks[st], Vs[st], qf, o, mrun, lrun, kmax_q, kt, q16, g);
         SK_TICK(te_);
         SK_ADD(2, tb_ - ta_); SK_ADD(3, tc_ - tb_); SK_ADD(6, td_ - tc_); SK_ADD(7, te_ - td_);
         st = st == 2 ? 0 : st + 1;
@@ -809,7 +826,7 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
         const float inv = (tq[u] < len && l > 0.f) ? 1.f / l : 0.f;
 #pragma unroll
         for (int dt = 0; dt < 4; dt++)
-            *reinterpret_cast<uint2*>(orow[u] + 16 * dt) = make_uint2(pack_bf16x2(o[u][dt][0] * inv, o[u][dt][1] * inv), pack_bf16x2(o[u][dt][2] * inv, o[u][dt][3] * inv));
+            *reinterpret_cast<uint2*>(orow[u] + 16 * dt) = make_uint2(OP::pack2(o[u][dt][0] * inv, o[u][dt][1] * inv), OP::pack2(o[u][dt][2] * inv, o[u][dt][3] * inv));
     }
 #ifdef CV2_STAMPS
     SK_STAMP(5);
@@ -826,7 +843,7 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
 // cycles), two 16 KB stages per group.  The tile body is att_est_tile<1, true> (the DMA form's key permutation): agreement with k_attn_est to
 // fp32 round-off, so -- like the other DMA forms -- it serves full-context calls only; a stream's chunk-masked recompute keeps the arithmetic
 // of its cached continuation.
-template <bool CACHE = false>
+template <class OP, bool CACHE = false>
 __global__ __launch_bounds__(1024) void k_attn_est_dma4(AttnEstArgs a) {
     constexpr int NW = 4, KSP = 4, RB = 64;
     __shared__ __attribute__((aligned(1024))) uint16_t Ts[KSP][2][2][64 * 64];          // [group][stage][K | V^T]: 128 KB
@@ -894,10 +911,10 @@ __global__ __launch_bounds__(1024) void k_attn_est_dma4(AttnEstArgs a) {
 #pragma unroll
     for (int dt = 0; dt < 4; dt++) o[0][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     dma(min(kgrp, last), 0);
-    bf16x8 qf[1][2];
+    v8_t<OP> qf[1][2];
 #pragma unroll
     for (int ks = 0; ks < 2; ks++)
-        qf[0][ks] = *reinterpret_cast<const bf16x8*>(a.qk + (size_t)(m0 + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
+        qf[0][ks] = *reinterpret_cast<const v8_t<OP>*>(a.qk + (size_t)(m0 + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) asm volatile("" : "+v"(qf[0][ks]));          // (the compiler's wait for q sits here, not inside the loop)
     int st = 0;
@@ -907,7 +924,7 @@ __global__ __launch_bounds__(1024) void k_attn_est_dma4(AttnEstArgs a) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                         // every wave's share of tile r has landed; every wave is done with tile r - 1
         dma(min(kt + KSP, last), st ^ 1);
-        att_est_tile<1, true>(Ts[kgrp][st][0], Ts[kgrp][st][1], qf, o, mrun, lrun, kmask_q, kt, q16, g);
+        att_est_tile<OP, 1, true>(Ts[kgrp][st][0], Ts[kgrp][st][1], qf, o, mrun, lrun, kmask_q, kt, q16, g);
         st ^= 1;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -945,7 +962,7 @@ __global__ __launch_bounds__(1024) void k_attn_est_dma4(AttnEstArgs a) {
     const float inv = (tq[0] < len && l > 0.f) ? 1.f / l : 0.f;
 #pragma unroll
     for (int dt = 0; dt < 4; dt++)
-        *reinterpret_cast<uint2*>(orow[0] + 16 * dt) = make_uint2(pack_bf16x2(o[0][dt][0] * inv, o[0][dt][1] * inv), pack_bf16x2(o[0][dt][2] * inv, o[0][dt][3] * inv));
+        *reinterpret_cast<uint2*>(orow[0] + 16 * dt) = make_uint2(OP::pack2(o[0][dt][0] * inv, o[0][dt][1] * inv), OP::pack2(o[0][dt][2] * inv, o[0][dt][3] * inv));
 }
 
 // =========================================================================== host side
@@ -1072,18 +1089,40 @@ static Layout make_layout(const std::vector<int>& lens, int lead = 0) {
     return L;
 }
 
+// fp16 engine: the time MLP's Linear layers (n <= 32 rows) on their packed fp16 weights (the LLM's skinny kernel, which a bf16 engine uses here,
+// is bf16-only and stays so).  One wave per output feature, lanes over K, fp16-rounded activation times fp16 weight summed in fp32; a few
+// microseconds at engine creation and per estimator-seam call, nothing of the Euler loop.
+__global__ __launch_bounds__(256) void k_linear_f16(const uint16_t* w, const float* bias, const float* x, float* out, int n, int k) {
+    const int o = blockIdx.x * 4 + (threadIdx.x >> 6), r = blockIdx.y, lane = threadIdx.x & 63;
+    if (o >= n) return;                                      // (wave-uniform)
+    const int KS = k / 32;
+    float acc = 0.f;
+    for (int kk = lane * 8; kk < k; kk += 512) {             // 8 consecutive k = one 16-byte run of the packed layout (include/cv2_amd.h)
+        const s16x8 wv = *reinterpret_cast<const s16x8*>(w + ((((size_t)(o >> 4) * KS + (kk >> 5)) * 4 + ((kk & 31) >> 3)) * 16 + (o & 15)) * 8);
+#pragma unroll
+        for (int j = 0; j < 8; j++) acc += OpF16::to_f32((uint16_t)wv[j]) * OpF16::to_f32(OpF16::from_f32(x[(size_t)r * k + kk + j]));
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) out[(size_t)r * n + o] = acc + (bias ? bias[o] : 0.f);
+}
+
 static int time_tables(cv2_flow* h, const float* t_dev, int n, float* tab_out, hipStream_t s) {
     // temb = Linear2(SiLU(Linear1(sinus(t)))) ; per resnet: Linear(Mish(temb))  (decoder.py:420-421, matcha decoder.py:58)
     float* e0 = h->tmp_t; float* e1 = e0 + 32 * 1024; float* e2 = e1 + 32 * 1024;
+    auto linear = [&](const cv2_lin& l, const float* x, float* y, int N, int K) -> int {
+        if (h->d.operands != CV2_OPERANDS_FP16) return skinny_gemm_launch(l.w, l.b, x, y, n, N, K, s);
+        hipLaunchKernelGGL(k_linear_f16, dim3(N / 4, n), dim3(256), 0, s, l.w, l.b, x, y, N, K);
+        return 0;
+    };
     hipLaunchKernelGGL(k_sinus, dim3(n), dim3(160), 0, s, t_dev, e0, n);
-    if (skinny_gemm_launch(h->w.time1.w, h->w.time1.b, e0, e1, n, 1024, 320, s)) return -1;
+    if (linear(h->w.time1, e0, e1, 1024, 320)) return -1;
     hipLaunchKernelGGL(k_act_inplace, dim3((n * 1024 + 255) / 256), dim3(256), 0, s, e1, n * 1024, ACT_SILU);
-    if (skinny_gemm_launch(h->w.time2.w, h->w.time2.b, e1, e2, n, 1024, 1024, s)) return -1;
+    if (linear(h->w.time2, e1, e2, 1024, 1024)) return -1;
     hipLaunchKernelGGL(k_act_inplace, dim3((n * 1024 + 255) / 256), dim3(256), 0, s, e2, n * 1024, ACT_MISH);
     // 14 resnets: down, mid 0..11, up ; output [n][14][256] -> skinny writes [n][256] with row stride 256, so go via e0
     for (int r = 0; r < 14; r++) {
         const cv2_resnet& rn = r == 0 ? h->w.down.rn : r == 13 ? h->w.up_blk.rn : h->w.mid[r - 1].rn;
-        if (skinny_gemm_launch(rn.mlp.w, rn.mlp.b, e2, e0, n, 256, 1024, s)) return -1;
+        if (linear(rn.mlp, e2, e0, 256, 1024)) return -1;
         CV2_HIP(hipMemcpy2DAsync(tab_out + r * 256, (size_t)14 * 256 * 4, e0, 256 * 4, 256 * 4, n, hipMemcpyDeviceToDevice, s));
     }
     CV2_LAUNCH_CHECK();
@@ -1094,6 +1133,7 @@ extern "C" int cv2_flow_create(const cv2_flow_dims* d, const cv2_flow_weights* w
     CV2_CHECK(d && w && ws && out, "cv2_flow_create: null argument");
     CV2_CHECK(d->max_rows % 128 == 0 && d->max_rows >= 256, "cv2_flow_create: max_rows must be a multiple of 128");
     CV2_CHECK(d->n_timesteps >= 1 && d->n_timesteps <= 31, "cv2_flow_create: n_timesteps out of range");
+    CV2_CHECK(d->operands == CV2_OPERANDS_BF16 || d->operands == CV2_OPERANDS_FP16, "cv2_flow_create: operands must be CV2_OPERANDS_BF16 or CV2_OPERANDS_FP16 (got %d)", d->operands);
     CV2_CHECK(ws_bytes >= cv2_flow_workspace_bytes(d), "cv2_flow_create: workspace too small");
     cv2_flow* h = new cv2_flow();
     h->d = *d; h->w = *w; h->ws = (char*)ws; h->ws_bytes = ws_bytes;
@@ -1143,26 +1183,28 @@ static int est_conv_tail(EstCtx& c, uint16_t* buf, int C) {
     return 0;
 }
 
+template <class OP>
 static int est_gemm(EstCtx& c, GemmArgs a, int cfg) {
     a.seq = c.L->tab(); a.mask = 1;
-    return gemm_launch_cfg(a, cfg, 1, true, c.s);
+    return gemm_launch_cfg<OP>(a, cfg, 1, true, c.s);
 }
 
 // resnet: A = bf16 input (guard-offset pointer) with C_in channels; leaves x (fp32, xf) and LN'd bf16 (lnb) for the first tblock
+template <class OP>
 static int est_resnet(EstCtx& c, const cv2_resnet& rn, int ridx, uint16_t* A, int cin, const cv2_ln& next_ln) {
     cv2_flow* h = c.h; const int M = c.L->rows;
     if (est_conv_tail(c, A, cin)) return -1;
     {   // res_conv 1x1
         GemmArgs a = gemm_args(A, cin, 0, rn.res.w, M, 256, cin);
         a.bias = rn.res.b; a.out_f32 = h->rf; a.ldo = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     {   // block1: conv k3 -> LN -> Mish -> + time embedding
         GemmArgs a = gemm_args(A, cin, -2, rn.conv1.w, M, 256, 3 * cin);
         a.bias = rn.conv1.b; a.ln1_g = rn.ln1.g; a.ln1_b = rn.ln1.b; a.ln1_eps = 1e-5f; a.act = ACT_MISH;
         a.rowadd = c.temb + ridx * 256; a.rowadd_ld = 0;
         a.out_bf16 = GB(h->hb, 256); a.ldo16 = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     if (est_conv_tail(c, GB(h->hb, 256), 256)) return -1;
     {   // block2 + residual; second LN = norm1 of the first transformer block
@@ -1170,7 +1212,7 @@ static int est_resnet(EstCtx& c, const cv2_resnet& rn, int ridx, uint16_t* A, in
         a.bias = rn.conv2.b; a.ln1_g = rn.ln2.g; a.ln1_b = rn.ln2.b; a.ln1_eps = 1e-5f; a.act = ACT_MISH;
         a.res = h->rf; a.ldres = 256; a.out_f32 = h->xf; a.ldo = 256;
         a.ln2_g = next_ln.g; a.ln2_b = next_ln.b; a.ln2_eps = 1e-5f; a.out_ln2 = GB(h->lnb, 256); a.ldo_ln2 = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     return 0;
 }
@@ -1186,6 +1228,7 @@ extern "C" int cv2_flow_debug_graph(int32_t on) { g_flow_graph = on < 0 ? -1 : (
 // transformer block; next_ln == null: last of its group -> bf16 copy of x goes to (xout, ldx).  have_qkv: the block's q / k / v^T are
 // there already (the previous block's tail kernel chained this block's QKV projection on); next_tb != null: the block that follows in the
 // group -- its QKV projection may be chained onto this block's tail (c.qkv_chained says whether it was).
+template <class OP>
 static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, uint16_t* xout, long ldx, const cv2_tblock* next_tb = nullptr) {
     cv2_flow* h = c.h; const int M = c.L->rows;
     const bool have_qkv = c.qkv_chained;
@@ -1198,7 +1241,7 @@ static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, ui
             CV2_CHECK(c.tb_i < INC_TBLOCKS, "flow: transformer block counter overflow");
             a.kvc = c.inc->kv; a.kvc_frames = c.inc->kv_frames; a.kvc_pos0 = c.inc->pos0; a.kvc_slot = (long)c.step * INC_TBLOCKS + c.tb_i; a.kvc_k0 = 512;
         }
-        if (est_gemm(c, a, 0)) return -1;
+        if (est_gemm<OP>(c, a, 0)) return -1;
     }
     {
         AttnEstArgs a{GB(h->qk, 1024), h->vt + GUARD, GB(h->att, 512), c.L->tab(), c.chunk, (long)(h->R + GUARD + 8), nullptr, nullptr, nullptr, 0};
@@ -1227,20 +1270,20 @@ static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, ui
         const int dma_dbg = g_att_dma.load();
         const bool dma = dma_dbg < 0 ? dma_env : dma_dbg != 0;
         if (c.inc) {
-            if (M / 128 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<2, true>), dim3(8, M / 128), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<2, 4, 1, true>), dim3(8, M / 128), dim3(256), 0, c.s, a); }
-            else if (M / 64 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<1, true>), dim3(8, M / 64), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<1, 4, 1, true>), dim3(8, M / 64), dim3(256), 0, c.s, a); }
-            else if (ksp4 && dma && dma4 && dma4s) hipLaunchKernelGGL(k_attn_est_dma4<true>, dim3(8, M / 64), dim3(1024), 0, c.s, a);
-            else if (ksp4) hipLaunchKernelGGL((k_attn_est<1, 4, 4, true>), dim3(8, M / 64), dim3(1024), 0, c.s, a);     // (9 .. 15 streams' chunks, 257 .. 511 blocks: two groups of a 512-thread block measured +1 %: 12 streams 165 -> 167 audio-s/s; not taken)
-            else hipLaunchKernelGGL((k_attn_est<1, 2, 2, true>), dim3(8, M / 32), dim3(256), 0, c.s, a);
+            if (M / 128 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 2, true>), dim3(8, M / 128), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 2, 4, 1, true>), dim3(8, M / 128), dim3(256), 0, c.s, a); }
+            else if (M / 64 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 1, true>), dim3(8, M / 64), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 1, true>), dim3(8, M / 64), dim3(256), 0, c.s, a); }
+            else if (ksp4 && dma && dma4 && dma4s) hipLaunchKernelGGL((k_attn_est_dma4<OP, true>), dim3(8, M / 64), dim3(1024), 0, c.s, a);
+            else if (ksp4) hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 4, true>), dim3(8, M / 64), dim3(1024), 0, c.s, a);     // (9 .. 15 streams' chunks, 257 .. 511 blocks: two groups of a 512-thread block measured +1 %: 12 streams 165 -> 167 audio-s/s; not taken)
+            else hipLaunchKernelGGL((k_attn_est<OP, 1, 2, 2, true>), dim3(8, M / 32), dim3(256), 0, c.s, a);
         }
-        else if (M / 128 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<2>), dim3(8, M / 128), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<2, 4>), dim3(8, M / 128), dim3(256), 0, c.s, a); }   // enough blocks to fill the chip twice
-        else if (M / 64 * 8 >= (c.chunk > 0 ? 512 : dma1_min)) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<1>), dim3(8, M / 64), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<1, 4>), dim3(8, M / 64), dim3(256), 0, c.s, a); }
+        else if (M / 128 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 2>), dim3(8, M / 128), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 2, 4>), dim3(8, M / 128), dim3(256), 0, c.s, a); }   // enough blocks to fill the chip twice
+        else if (M / 64 * 8 >= (c.chunk > 0 ? 512 : dma1_min)) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 1>), dim3(8, M / 64), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 1, 4>), dim3(8, M / 64), dim3(256), 0, c.s, a); }
         // below 512 blocks: the four-group form with its tiles by LDS DMA.  Chunk-masked (streaming) calls take it together with their cached
         // continuation (dma4s) over this whole range, so that recomputed and cached chunks of a stream keep ONE arithmetic whatever their row counts
-        else if (ksp4 && dma && dma4 && (c.chunk == 0 || dma4s)) hipLaunchKernelGGL(k_attn_est_dma4<false>, dim3(8, M / 64), dim3(1024), 0, c.s, a);
-        else if (ksp4 && (M / 64 * 8 <= 256 || !ksp42 || c.chunk > 0)) hipLaunchKernelGGL((k_attn_est<1, 4, 4>), dim3(8, M / 64), dim3(1024), 0, c.s, a);   // one utterance: the keys split over four wave groups of a 64-row block
-        else if (ksp4) hipLaunchKernelGGL((k_attn_est<1, 4, 2>), dim3(8, M / 64), dim3(512), 0, c.s, a);     // more blocks than CUs (a 1024-thread block fills one): two groups, two blocks per CU
-        else hipLaunchKernelGGL((k_attn_est<1, 2, 2>), dim3(8, M / 32), dim3(256), 0, c.s, a);       // (over two groups of a 32-row block)
+        else if (ksp4 && dma && dma4 && (c.chunk == 0 || dma4s)) hipLaunchKernelGGL((k_attn_est_dma4<OP, false>), dim3(8, M / 64), dim3(1024), 0, c.s, a);
+        else if (ksp4 && (M / 64 * 8 <= 256 || !ksp42 || c.chunk > 0)) hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 4>), dim3(8, M / 64), dim3(1024), 0, c.s, a);   // one utterance: the keys split over four wave groups of a 64-row block
+        else if (ksp4) hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 2>), dim3(8, M / 64), dim3(512), 0, c.s, a);     // more blocks than CUs (a 1024-thread block fills one): two groups, two blocks per CU
+        else hipLaunchKernelGGL((k_attn_est<OP, 1, 2, 2>), dim3(8, M / 32), dim3(256), 0, c.s, a);       // (over two groups of a 32-row block)
     }
     static const bool tail_rows_off = getenv("CV2_FLOW_TAIL_ROWS") && getenv("CV2_FLOW_TAIL_ROWS")[0] == '0';     // A/B switch (diagnostics)
     static const long tail_rows_min = getenv("CV2_FLOW_TAIL_ROWS_MIN") ? atol(getenv("CV2_FLOW_TAIL_ROWS_MIN")) : 96;    // 64-row tiles from which the 64-row blocks are used (8 streaming chunks: 192 -> 184 ms first chunk)
@@ -1256,22 +1299,22 @@ static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, ui
         t.seq = c.L->tab(); t.M_valid = M;
         t.part = h->tail_part; t.ticket = h->tail_ticket;
         t.row0 = c.inc && M > INC_LEAD ? INC_LEAD : 0;           // (cached chunks: skip the lead panels, see TailArgs::row0)
-        if ((long)(M / 64) < tail_rows_min) return tail_panel_go(t, M, c.s);
+        if ((long)(M / 64) < tail_rows_min) return tail_panel_go<OP>(t, M, c.s);
         // batches: k_tail_rows2 (round 5); CV2_FLOW_TAIL_ROWS2=0: k_tail_rows<4>, =1: k_tail_rows2 without the chained QKV projection (A/B, diagnostics)
         static const int rows2 = getenv("CV2_FLOW_TAIL_ROWS2") ? atoi(getenv("CV2_FLOW_TAIL_ROWS2")) : 2;
-        if (rows2 == 0) return tail_rows_go(t, M, c.s);
+        if (rows2 == 0) return tail_rows_go<OP>(t, M, c.s);
         const bool chain = rows2 >= 2 && next_tb && next_ln && !c.inc;      // (cached streaming chunks file their keys / values in the QKV GEMM's epilogue)
         if (chain) {
             t.Wqkv = next_tb->qkv.w; t.qk = GB(h->qk, 1024); t.vt = h->vt + GUARD; t.vt_ld = h->R + GUARD + 8;
             c.qkv_chained = true;
         }
-        return tail_rows2_go(t, M, chain, c.s);
+        return tail_rows2_go<OP>(t, M, chain, c.s);
     }
     {
         GemmArgs a = gemm_args(GB(h->att, 512), 512, 0, tb.out.w, M, 256, 512);
         a.bias = tb.out.b; a.res = h->xf; a.ldres = 256; a.out_f32 = h->xf; a.ldo = 256;
         a.ln2_g = tb.norm3.g; a.ln2_b = tb.norm3.b; a.ln2_eps = 1e-5f; a.out_ln2 = GB(h->lnb, 256); a.ldo_ln2 = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     {
         GemmArgs a = gemm_args(GB(h->ff, 1024), 1024, 0, tb.ff2.w, M, 256, 1024);
@@ -1284,62 +1327,65 @@ static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, ui
         }
         GemmArgs a1 = gemm_args(GB(h->lnb, 256), 256, 0, tb.ff1.w, M, 1024, 256);
         a1.bias = tb.ff1.b; a1.act = ACT_GELU; a1.out_bf16 = GB(h->ff, 1024); a1.ldo16 = 1024;
-        if (est_gemm(c, a1, 0)) return -1;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a1, 0)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     return 0;
 }
 
+template <class OP>
 static int est_block(EstCtx& c, const cv2_unet_block& b, int ridx, uint16_t* A, int cin, uint16_t* xout, long ldx) {
-    if (est_resnet(c, b.rn, ridx, A, cin, b.tb[0].norm1)) return -1;
+    if (est_resnet<OP>(c, b.rn, ridx, A, cin, b.tb[0].norm1)) return -1;
     for (int j = 0; j < 4; j++)
-        if (est_tblock(c, b.tb[j], j < 3 ? &b.tb[j + 1].norm1 : nullptr, xout, ldx, j < 3 ? &b.tb[j + 1] : nullptr)) return -1;
+        if (est_tblock<OP>(c, b.tb[j], j < 3 ? &b.tb[j + 1].norm1 : nullptr, xout, ldx, j < 3 ? &b.tb[j + 1] : nullptr)) return -1;
     return 0;
 }
 
 // a0 (bf16 [rows][320]) -> vf (fp32 [rows][80])      CausalConditionalDecoder.forward, decoder.py:405-494
+template <class OP>
 static int estimator_core(EstCtx& c) {
     cv2_flow* h = c.h; const int M = c.L->rows;
     const cv2_flow_weights& w = h->w;
     c.conv_i = 0; c.tb_i = 0;
-    if (est_block(c, w.down, 0, GB(h->a0, 320), 320, GB(h->xa, 256), 256)) return -1;
+    if (est_block<OP>(c, w.down, 0, GB(h->a0, 320), 320, GB(h->xa, 256), 256)) return -1;
     // skip connection: xa -> cat[:, 256:512]
     CV2_HIP(hipMemcpy2DAsync(GB(h->cat, 512) + 256, 512 * 2, GB(h->xa, 256), 256 * 2, 256 * 2, M, hipMemcpyDeviceToDevice, c.s));
     if (est_conv_tail(c, GB(h->xa, 256), 256)) return -1;
     {   // downsample tail: CausalConv1d(256,256,3)
         GemmArgs a = gemm_args(GB(h->xa, 256), 256, -2, w.down.tail.w, M, 256, 768);
         a.bias = w.down.tail.b; a.out_bf16 = GB(h->xbuf, 256); a.ldo16 = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     for (int i = 0; i < 12; i++) {
         uint16_t* A = i == 0 ? GB(h->xbuf, 256) : GB(h->xa, 256);
         uint16_t* xo = i == 11 ? GB(h->cat, 512) : GB(h->xa, 256);
-        if (est_block(c, w.mid[i], 1 + i, A, 256, xo, i == 11 ? 512 : 256)) return -1;
+        if (est_block<OP>(c, w.mid[i], 1 + i, A, 256, xo, i == 11 ? 512 : 256)) return -1;
     }
-    if (est_block(c, w.up_blk, 13, GB(h->cat, 512), 512, GB(h->xa, 256), 256)) return -1;
+    if (est_block<OP>(c, w.up_blk, 13, GB(h->cat, 512), 512, GB(h->xa, 256), 256)) return -1;
     if (est_conv_tail(c, GB(h->xa, 256), 256)) return -1;
     {   // upsample tail
         GemmArgs a = gemm_args(GB(h->xa, 256), 256, -2, w.up_blk.tail.w, M, 256, 768);
         a.bias = w.up_blk.tail.b; a.out_bf16 = GB(h->xbuf, 256); a.ldo16 = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     if (est_conv_tail(c, GB(h->xbuf, 256), 256)) return -1;
     {   // final_block: conv -> LN -> Mish
         GemmArgs a = gemm_args(GB(h->xbuf, 256), 256, -2, w.final_conv.w, M, 256, 768);
         a.bias = w.final_conv.b; a.ln1_g = w.final_ln.g; a.ln1_b = w.final_ln.b; a.ln1_eps = 1e-5f; a.act = ACT_MISH;
         a.out_bf16 = GB(h->hb, 256); a.ldo16 = 256;
-        if (est_gemm(c, a, 1)) return -1;
+        if (est_gemm<OP>(c, a, 1)) return -1;
     }
     {   // final_proj 256 -> 80 (weights padded to 128 rows)
         GemmArgs a = gemm_args(GB(h->hb, 256), 256, 0, w.final_proj.w, M, 128, 256);
         a.bias = w.final_proj.b; a.out_f32 = h->vf; a.ldo = 80; a.n_store = 80;
-        if (est_gemm(c, a, 0)) return -1;
+        if (est_gemm<OP>(c, a, 0)) return -1;
     }
     CV2_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int cv2_flow_estimator(cv2_flow* h, float* x, const float* mask, const float* mu, const float* t, const float* spks,
+template <class OP>
+static int cv2_flow_estimator_t(cv2_flow* h, float* x, const float* mask, const float* mu, const float* t, const float* spks,
                                   const float* cond, int32_t T, int32_t streaming, void* stream) {
     CV2_CHECK(h && x && mu && t && spks && cond, "cv2_flow_estimator: null argument");
     (void)mask;   // the reference always passes an all-ones mask of length T (flow.py:272); lengths come from T
@@ -1351,9 +1397,9 @@ extern "C" int cv2_flow_estimator(cv2_flow* h, float* x, const float* mask, cons
     float* tab = h->temb_tab + (size_t)31 * 14 * 256;
     if (time_tables(h, t, 1, tab, s)) return -1;
     SeamPackArgs p{x, mu, spks, cond, T, L.start[1], GB(h->a0, 320), L.rows};
-    hipLaunchKernelGGL(k_seam_pack, dim3(((long)L.rows * 320 + 255) / 256), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_seam_pack<OP>, dim3(((long)L.rows * 320 + 255) / 256), dim3(256), 0, s, p);
     EstCtx c{h, &L, tab, streaming ? 50 : 0, s};
-    if (estimator_core(c)) return -1;
+    if (estimator_core<OP>(c)) return -1;
     hipLaunchKernelGGL(k_seam_unpack, dim3((2L * 80 * T + 255) / 256), dim3(256), 0, s, (const float*)h->vf, x, (int)T, L.start[1]);
     CV2_LAUNCH_CHECK();
     return 0;
@@ -1393,6 +1439,7 @@ __global__ __launch_bounds__(256) void k_enc_append(EncAppendArgs a) {
 // left context of a causal convolution: rows [start - nrep * 2, start) of `buf` <- the cached two rows (each repeated nrep times: the
 // upsampled signal repeats a token row twice), and this call's last two rows of `src` (bf16 `buf` itself, or the fp32 stage output) -> cache
 struct EncTailArgs { uint16_t* buf; const float* src_f32; const uint16_t* src_b16; long src_start; int start, n_src, n0, nrep; const uint16_t* rd; uint16_t* wr; };
+template <class OP>
 __global__ __launch_bounds__(256) void k_enc_tail(EncTailArgs a) {
     for (int e = threadIdx.x; e < 2 * 512; e += 256) {
         const int j = e >> 9, c = e & 511;
@@ -1400,7 +1447,7 @@ __global__ __launch_bounds__(256) void k_enc_tail(EncTailArgs a) {
         for (int r = 0; r < a.nrep; r++) a.buf[(long)(a.start - 2 * a.nrep + j * a.nrep + r) * 512 + c] = o;
         const int pos = a.n_src - 2 + j;                         // source row of the new tail (pos < 0: fewer than two new rows)
         uint16_t v;
-        if (pos >= 0) v = a.src_f32 ? (uint16_t)(pack_bf16x2(a.src_f32[(a.src_start + pos) * 512 + c], 0.f) & 0xffffu) : a.src_b16[(a.src_start + pos) * 512 + c];     // (k_repeat2's conversion)
+        if (pos >= 0) v = a.src_f32 ? (uint16_t)(OP::pack2(a.src_f32[(a.src_start + pos) * 512 + c], 0.f) & 0xffffu) : a.src_b16[(a.src_start + pos) * 512 + c];     // (k_repeat2's conversion)
         else v = pos == -1 && a.n0 > 0 ? a.rd[512 + c] : (uint16_t)0;
         a.wr[j * 512 + c] = v;
     }
@@ -1427,25 +1474,28 @@ struct EncInc {                                   // cached streaming: one entry
 };
 struct EncCtx { cv2_flow* h; const Layout* L; int chunk; hipStream_t s; const EncInc* inc = nullptr; int layer = 0; int rate = 1; };
 
+template <class OP>
 static int enc_gemm(EncCtx& c, GemmArgs a, int cfg) {
     a.seq = c.L->tab(); a.mask = 1;
-    return gemm_launch_cfg(a, cfg, 1, true, c.s);
+    return gemm_launch_cfg<OP>(a, cfg, 1, true, c.s);
 }
+template <class OP>
 static int enc_ln(EncCtx& c, const float* x, const cv2_ln& ln, float eps, float scale, float* of, uint16_t* ob) {
     LnArgs a{x, 512, 512, ln.g, ln.b, eps, scale, c.L->tab(), c.L->rows, of, 512, ob, 512};
-    hipLaunchKernelGGL(k_layernorm<8>, dim3((c.L->rows + 3) / 4), dim3(256), 0, c.s, a);
+    hipLaunchKernelGGL((k_layernorm<8, OP>), dim3((c.L->rows + 3) / 4), dim3(256), 0, c.s, a);
     return 0;
 }
 
 // one ConformerEncoderLayer over x (fp32 e_x, in place)      encoder_layer.py:160-236, attention.py:249-330
+template <class OP>
 static int conformer_layer(EncCtx& c, const cv2_conformer& cl) {
     cv2_flow* h = c.h; const int M = c.L->rows; const long RG = h->R + GUARD + 8;
-    enc_ln(c, h->e_x, cl.norm_mha, 1e-12f, 1.f, nullptr, GB(h->e_ln, 512));
+    enc_ln<OP>(c, h->e_x, cl.norm_mha, 1e-12f, 1.f, nullptr, GB(h->e_ln, 512));
     {
         GemmArgs a = gemm_args(GB(h->e_ln, 512), 512, 0, cl.qkv.w, M, 2048, 512);
         a.bias = cl.qkv.b; a.out_bf16 = GB(h->e_qkv, 1536); a.ldo16 = 1536; a.n_store = 1536;
         a.vt = h->e_vt + GUARD; a.vt_ld = RG; a.vt_n0 = 1536;
-        if (enc_gemm(c, a, 0)) return -1;
+        if (enc_gemm<OP>(c, a, 0)) return -1;
     }
     int pos_T = -1;
     for (int q = 0; c.inc && q < c.L->S; q++) {
@@ -1462,10 +1512,10 @@ static int conformer_layer(EncCtx& c, const cv2_conformer& cl) {
             hipLaunchKernelGGL(k_enc_append, dim3(((long)nn * 512 + 255) / 256, 2), dim3(256), 0, c.s, a);
         }
         if (T != pos_T) {
-            hipLaunchKernelGGL(k_pos_emb, dim3(P), dim3(256), 0, c.s, h->pos, T, P);
+            hipLaunchKernelGGL(k_pos_emb<OP>, dim3(P), dim3(256), 0, c.s, h->pos, T, P);
             GemmArgs a = gemm_args(h->pos, 512, 0, cl.pos.w, P, 512, 512);
             a.out_bf16 = h->posp; a.ldo16 = 512;
-            if (gemm_launch_cfg(a, 0, 1, true, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 1, true, c.s)) return -1;
             pos_T = T;
         }
         const uint16_t* qkv = GB(h->e_qkv, 1536) + (size_t)r0 * 1536;
@@ -1473,32 +1523,32 @@ static int conformer_layer(EncCtx& c, const cv2_conformer& cl) {
             GemmArgs a = gemm_args(qkv, 1536, 0, Kc, Mp, Tk, 64);
             a.a_bstride = 64; a.ldw = 512; a.w_bstride = 64;
             a.out_f32 = h->ac; a.ldo = Tk; a.o_bstride = (long)Mp * Tk;
-            if (gemm_launch_cfg(a, 0, 8, false, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 8, false, c.s)) return -1;
         }
         {   // bd[h] = (q + v) p^T
             GemmArgs a = gemm_args(qkv + 512, 1536, 0, h->posp, Mp, P, 64);
             a.a_bstride = 64; a.ldw = 512; a.w_bstride = 64;
             a.out_f32 = h->bd; a.ldo = P; a.o_bstride = (long)Mp * P;
-            if (gemm_launch_cfg(a, 0, 8, false, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 8, false, c.s)) return -1;
         }
         {
             RelSmArgs a{h->ac, h->bd, h->probs, T, Mp, Tk, P, c.chunk, n0, nn};
-            hipLaunchKernelGGL(k_relsoftmax, dim3(Mp, 8), dim3(256), (size_t)Tk * 4, c.s, a);
+            hipLaunchKernelGGL(k_relsoftmax<OP>, dim3(Mp, 8), dim3(256), (size_t)Tk * 4, c.s, a);
         }
         {   // att[:, h*64:(h+1)*64] = probs[h] V[h] from the cache
             GemmArgs a = gemm_args(h->probs, Tk, 0, VTc, Mp, 64, Tk);
             a.a_bstride = (long)Mp * Tk; a.ldw = cap; a.w_bstride = 64 * cap;
             a.out_bf16 = GB(h->e_att, 512) + (size_t)r0 * 512; a.ldo16 = 512; a.o16_bstride = 64;
-            if (gemm_launch_cfg(a, 2, 8, false, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 2, 8, false, c.s)) return -1;
         }
     }
     for (int q = 0; !c.inc && q < c.L->S; q++) {
         const int T = c.L->len[q], r0 = c.L->start[q], Tp = pad_rows(T), P = (2 * T - 1 + 127) / 128 * 128;
         if (T != pos_T) {       // linear_pos(pos_emb(T)) for this layer
-            hipLaunchKernelGGL(k_pos_emb, dim3(P), dim3(256), 0, c.s, h->pos, T, P);
+            hipLaunchKernelGGL(k_pos_emb<OP>, dim3(P), dim3(256), 0, c.s, h->pos, T, P);
             GemmArgs a = gemm_args(h->pos, 512, 0, cl.pos.w, P, 512, 512);
             a.out_bf16 = h->posp; a.ldo16 = 512;
-            if (gemm_launch_cfg(a, 0, 1, true, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 1, true, c.s)) return -1;
             pos_T = T;
         }
         const uint16_t* qkv = GB(h->e_qkv, 1536) + (size_t)r0 * 1536;
@@ -1506,40 +1556,40 @@ static int conformer_layer(EncCtx& c, const cv2_conformer& cl) {
             GemmArgs a = gemm_args(qkv, 1536, 0, qkv + 1024, Tp, Tp, 64);
             a.a_bstride = 64; a.ldw = 1536; a.w_bstride = 64;
             a.out_f32 = h->ac; a.ldo = Tp; a.o_bstride = (long)Tp * Tp;
-            if (gemm_launch_cfg(a, 0, 8, false, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 8, false, c.s)) return -1;
         }
         {   // bd[h] = (q + v) p^T
             GemmArgs a = gemm_args(qkv + 512, 1536, 0, h->posp, Tp, P, 64);
             a.a_bstride = 64; a.ldw = 512; a.w_bstride = 64;
             a.out_f32 = h->bd; a.ldo = P; a.o_bstride = (long)Tp * P;
-            if (gemm_launch_cfg(a, 0, 8, false, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 8, false, c.s)) return -1;
         }
         {
             RelSmArgs a{h->ac, h->bd, h->probs, T, Tp, Tp, P, c.chunk, 0, T};
-            hipLaunchKernelGGL(k_relsoftmax, dim3(Tp, 8), dim3(256), (size_t)Tp * 4, c.s, a);
+            hipLaunchKernelGGL(k_relsoftmax<OP>, dim3(Tp, 8), dim3(256), (size_t)Tp * 4, c.s, a);
         }
         {   // att[:, h*64:(h+1)*64] = probs[h] V[h]
             GemmArgs a = gemm_args(h->probs, Tp, 0, h->e_vt + GUARD + r0, Tp, 64, Tp);
             a.a_bstride = (long)Tp * Tp; a.ldw = RG; a.w_bstride = 64 * RG;
             a.out_bf16 = GB(h->e_att, 512) + (size_t)r0 * 512; a.ldo16 = 512; a.o16_bstride = 64;
-            if (gemm_launch_cfg(a, 2, 8, false, c.s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 2, 8, false, c.s)) return -1;
         }
     }
     {
         GemmArgs a = gemm_args(GB(h->e_att, 512), 512, 0, cl.out.w, M, 512, 512);
         a.bias = cl.out.b; a.res = h->e_x; a.ldres = 512; a.out_f32 = h->e_x; a.ldo = 512;
-        if (enc_gemm(c, a, 0)) return -1;
+        if (enc_gemm<OP>(c, a, 0)) return -1;
     }
-    enc_ln(c, h->e_x, cl.norm_ff, 1e-12f, 1.f, nullptr, GB(h->e_ln, 512));
+    enc_ln<OP>(c, h->e_x, cl.norm_ff, 1e-12f, 1.f, nullptr, GB(h->e_ln, 512));
     {
         GemmArgs a = gemm_args(GB(h->e_ln, 512), 512, 0, cl.w1.w, M, 2048, 512);
         a.bias = cl.w1.b; a.act = ACT_SILU; a.out_bf16 = GB(h->e_ff, 2048); a.ldo16 = 2048;
-        if (enc_gemm(c, a, 0)) return -1;
+        if (enc_gemm<OP>(c, a, 0)) return -1;
     }
     {
         GemmArgs a = gemm_args(GB(h->e_ff, 2048), 2048, 0, cl.w2.w, M, 512, 2048);
         a.bias = cl.w2.b; a.res = h->e_x; a.ldres = 512; a.out_f32 = h->e_x; a.ldo = 512;
-        if (enc_gemm(c, a, 0)) return -1;
+        if (enc_gemm<OP>(c, a, 0)) return -1;
     }
     CV2_LAUNCH_CHECK();
     return 0;
@@ -1550,6 +1600,7 @@ static int conformer_layer(EncCtx& c, const cv2_conformer& cl) {
 // LA = layout with the embed-stage lengths, LT = token-rate layout (T), L2 = mel-rate layout (2T); same starts for LA/LT.
 // inc != null (cached streaming): the layouts hold only the NEW tokens / frames of every sequence (after INC_LEAD lead rows), the rest
 // comes from the sequences' encoder caches.
+template <class OP>
 static int encoder_core(cv2_flow* h, Layout& LA, Layout& LT, Layout& L2, int streaming, float* out_f32, hipStream_t s, const EncInc* inc = nullptr) {
     const cv2_flow_weights& w = h->w;
     const float SQ = sqrtf(512.f);
@@ -1562,39 +1613,39 @@ static int encoder_core(cv2_flow* h, Layout& LA, Layout& LT, Layout& L2, int str
     {   // embed: Linear -> LayerNorm(1e-5) -> * sqrt(512)     subsampling.py:69-113, embedding.py:268
         GemmArgs a = gemm_args(GB(h->e_a, 512), 512, 0, w.embed.w, M, 512, 512);
         a.bias = w.embed.b; a.out_f32 = h->e_tmp; a.ldo = 512;
-        if (enc_gemm(ca, a, 0)) return -1;
-        enc_ln(ca, h->e_tmp, w.embed_ln, 1e-5f, SQ, h->e_x, GB(h->e_b, 512));
+        if (enc_gemm<OP>(ca, a, 0)) return -1;
+        enc_ln<OP>(ca, h->e_tmp, w.embed_ln, 1e-5f, SQ, h->e_x, GB(h->e_b, 512));
     }
     {   // pre_lookahead: conv k4 over [t, t+3] -> leaky_relu -> causal conv k3 -> + x      upsample_encoder.py:82-102
         GemmArgs a = gemm_args(GB(h->e_b, 512), 512, 0, w.pre1.w, M, 512, 2048);
         a.bias = w.pre1.b; a.act = ACT_LRELU; a.act_slope = 0.01f; a.out_bf16 = GB(h->e_a, 512); a.ldo16 = 512;
-        if (enc_gemm(ct, a, 0)) return -1;
+        if (enc_gemm<OP>(ct, a, 0)) return -1;
         for (int q = 0; inc && q < LT.S; q++) {      // conv2's left context: the previous call's last two conv1 outputs
             EncTailArgs t{GB(h->e_a, 512), nullptr, GB(h->e_a, 512), LT.start[q], LT.start[q], LT.len[q], inc->n0_tok[q], 1, tail(q, 0, false), tail(q, 0, true)};
-            hipLaunchKernelGGL(k_enc_tail, dim3(1), dim3(256), 0, s, t);
+            hipLaunchKernelGGL(k_enc_tail<OP>, dim3(1), dim3(256), 0, s, t);
         }
         GemmArgs b = gemm_args(GB(h->e_a, 512), 512, -2, w.pre2.w, M, 512, 1536);
         b.bias = w.pre2.b; b.res = h->e_x; b.ldres = 512; b.out_f32 = h->e_x; b.ldo = 512;
-        if (enc_gemm(ct, b, 0)) return -1;
+        if (enc_gemm<OP>(ct, b, 0)) return -1;
     }
-    for (int i = 0; i < 6; i++) { ct.layer = i; if (conformer_layer(ct, w.enc[i])) return -1; }
+    for (int i = 0; i < 6; i++) { ct.layer = i; if (conformer_layer<OP>(ct, w.enc[i])) return -1; }
     {   // Upsample1D: nearest x2, left pad 4, conv k5   upsample_encoder.py:37-63 ; then up_embed
         RepeatArgs r{h->e_x, LT.tab(), L2.tab(), L2.rows, GB(h->e_a, 512)};
-        hipLaunchKernelGGL(k_repeat2, dim3((L2.rows + 1) / 2), dim3(256), 0, s, r);
+        hipLaunchKernelGGL(k_repeat2<OP>, dim3((L2.rows + 1) / 2), dim3(256), 0, s, r);
         for (int q = 0; inc && q < LT.S; q++) {      // the k = 5 conv's left context: the previous call's last two token rows, each repeated twice
             EncTailArgs t{GB(h->e_a, 512), h->e_x, nullptr, LT.start[q], L2.start[q], LT.len[q], inc->n0_tok[q], 2, tail(q, 1, false), tail(q, 1, true)};
-            hipLaunchKernelGGL(k_enc_tail, dim3(1), dim3(256), 0, s, t);
+            hipLaunchKernelGGL(k_enc_tail<OP>, dim3(1), dim3(256), 0, s, t);
         }
         GemmArgs a = gemm_args(GB(h->e_a, 512), 512, -4, w.up_conv.w, L2.rows, 512, 2560);
         a.bias = w.up_conv.b; a.out_bf16 = GB(h->e_b, 512); a.ldo16 = 512;
-        if (enc_gemm(c2, a, 0)) return -1;
+        if (enc_gemm<OP>(c2, a, 0)) return -1;
         GemmArgs b = gemm_args(GB(h->e_b, 512), 512, 0, w.up_embed.w, L2.rows, 512, 512);
         b.bias = w.up_embed.b; b.out_f32 = h->e_tmp; b.ldo = 512;
-        if (enc_gemm(c2, b, 0)) return -1;
-        enc_ln(c2, h->e_tmp, w.up_embed_ln, 1e-5f, SQ, h->e_x, nullptr);
+        if (enc_gemm<OP>(c2, b, 0)) return -1;
+        enc_ln<OP>(c2, h->e_tmp, w.up_embed_ln, 1e-5f, SQ, h->e_x, nullptr);
     }
-    for (int i = 0; i < 4; i++) { c2.layer = 6 + i; if (conformer_layer(c2, w.up[i])) return -1; }
-    enc_ln(c2, h->e_x, w.after_norm, 1e-5f, 1.f, out_f32, GB(h->e_ln, 512));
+    for (int i = 0; i < 4; i++) { c2.layer = 6 + i; if (conformer_layer<OP>(c2, w.up[i])) return -1; }
+    enc_ln<OP>(c2, h->e_x, w.after_norm, 1e-5f, 1.f, out_f32, GB(h->e_ln, 512));
     CV2_LAUNCH_CHECK();
     return 0;
 }
@@ -1606,7 +1657,8 @@ static int check_rows(cv2_flow* h, const Layout& L, const char* who) {
     return 0;
 }
 
-extern "C" int cv2_flow_encoder(cv2_flow* h, const float* xs, int32_t T, const float* context, int32_t streaming, float* out, void* stream) {
+template <class OP>
+static int cv2_flow_encoder_t(cv2_flow* h, const float* xs, int32_t T, const float* context, int32_t streaming, float* out, void* stream) {
     CV2_CHECK(h && xs && out && T >= 1, "cv2_flow_encoder: bad argument");
     hipStream_t s = (hipStream_t)stream;
     Layout LT = make_layout({T}), L2 = make_layout({2 * T});
@@ -1620,14 +1672,15 @@ extern "C" int cv2_flow_encoder(cv2_flow* h, const float* xs, int32_t T, const f
     CV2_HIP(hipMemcpyAsync(off, &zero, sizeof(int), hipMemcpyHostToDevice, s));
     CV2_HIP(hipStreamSynchronize(s));
     CastArgs ca{xs, GB(h->e_a, 512), LT.tab(), LT.rows, 512, off};
-    hipLaunchKernelGGL(k_cast_rows, dim3(((long)LT.rows * 128 + 255) / 256), dim3(256), 0, s, ca);
-    if (context) hipLaunchKernelGGL(k_ctx_rows, dim3(6), dim3(256), 0, s, context, GB(h->e_a, 512) + (size_t)T * 512);
-    if (encoder_core(h, LA, LT, L2, streaming, h->e_tmp, s)) return -1;
+    hipLaunchKernelGGL(k_cast_rows<OP>, dim3(((long)LT.rows * 128 + 255) / 256), dim3(256), 0, s, ca);
+    if (context) hipLaunchKernelGGL(k_ctx_rows<OP>, dim3(6), dim3(256), 0, s, context, GB(h->e_a, 512) + (size_t)T * 512);
+    if (encoder_core<OP>(h, LA, LT, L2, streaming, h->e_tmp, s)) return -1;
     CV2_HIP(hipMemcpyAsync(out, h->e_tmp, (size_t)2 * T * 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
-extern "C" int cv2_flow_inference(cv2_flow* h, const cv2_flow_utt* utts, int32_t U, int32_t streaming, int32_t finalize, void* stream) {
+template <class OP>
+static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U, int32_t streaming, int32_t finalize, void* stream) {
     CV2_CHECK(h && utts && U >= 1, "cv2_flow_inference: bad argument");
     CV2_CHECK(2 * U <= h->d.max_seqs, "cv2_flow_inference: %d utterances exceed max_seqs/2", U);
     hipStream_t s = (hipStream_t)stream;
@@ -1666,12 +1719,12 @@ extern "C" int cv2_flow_inference(cv2_flow* h, const cv2_flow_utt* utts, int32_t
         hipLaunchKernelGGL(k_spk, dim3(U), dim3(128), 0, s, sp);
         // token embedding rows
         EmbedPtrArgs ea{(const int* const*)(dp + 3 * U), h->w.input_embedding, LA.tab(), LA.rows, GB(h->e_a, 512)};
-        hipLaunchKernelGGL(k_embed_tokens_ptr, dim3((LA.rows + 1) / 2), dim3(256), 0, s, ea);
-        if (encoder_core(h, LA, LT, L2, streaming, nullptr, s)) return -1;
+        hipLaunchKernelGGL(k_embed_tokens_ptr<OP>, dim3((LA.rows + 1) / 2), dim3(256), 0, s, ea);
+        if (encoder_core<OP>(h, LA, LT, L2, streaming, nullptr, s)) return -1;
         {   // encoder_proj 512 -> 80 -> mu
             GemmArgs a = gemm_args(GB(h->e_ln, 512), 512, 0, h->w.enc_proj.w, L2.rows, 128, 512);
             a.bias = h->w.enc_proj.b; a.out_f32 = h->mu; a.ldo = 80; a.n_store = 80; a.seq = L2.tab(); a.mask = 1;
-            if (gemm_launch_cfg(a, 0, 1, true, s)) return -1;
+            if (gemm_launch_cfg<OP>(a, 0, 1, true, s)) return -1;
         }
         // Euler loop (flow_matching.py:91-121)
         EstCtx c{h, &LE, nullptr, streaming ? 50 : 0, s};
@@ -1679,15 +1732,15 @@ extern "C" int cv2_flow_inference(cv2_flow* h, const cv2_flow_utt* utts, int32_t
             PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, st == 0 ? h->w.rand_noise : nullptr,
                        st == 0 ? nullptr : h->vf, st == 0 ? 0.f : h->dt_host[st - 1], h->d.cfg_rate, L2.tab(), RU, U, GB(h->a0, 320),
                        nullptr, nullptr, RU, 0};
-            hipLaunchKernelGGL(k_euler_pack, dim3(((long)RU * 20 + 255) / 256), dim3(256), 0, s, p);
+            hipLaunchKernelGGL(k_euler_pack<OP>, dim3(((long)RU * 20 + 255) / 256), dim3(256), 0, s, p);
             c.temb = h->temb_tab + (size_t)st * 14 * 256;
-            if (estimator_core(c)) return -1;
+            if (estimator_core<OP>(c)) return -1;
         }
         {   // last update without a following pack: reuse k_euler_pack (a0 is scratch now)
             const int st = h->d.n_timesteps;
             PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, nullptr, h->vf, h->dt_host[st - 1], h->d.cfg_rate,
                        L2.tab(), RU, U, GB(h->a0, 320), nullptr, nullptr, RU, 0};
-            hipLaunchKernelGGL(k_euler_pack, dim3(((long)RU * 20 + 255) / 256), dim3(256), 0, s, p);
+            hipLaunchKernelGGL(k_euler_pack<OP>, dim3(((long)RU * 20 + 255) / 256), dim3(256), 0, s, p);
         }
         int maxn2 = 1;
         for (int u = 0; u < U; u++) maxn2 = std::max(maxn2, lens2[u] - utts[u].n_prompt_feat);
@@ -1809,7 +1862,8 @@ extern "C" int cv2_flow_cache_copy(const cv2_flow* h, const void* src, int32_t s
     return 0;
 }
 
-extern "C" int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, int32_t U, int32_t finalize,
+template <class OP>
+static int cv2_flow_inference_chunk_t(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, int32_t U, int32_t finalize,
                                         void* stream) {
     CV2_CHECK(h && utts && refs && U >= 1, "cv2_flow_inference_chunk: bad argument");
     CV2_CHECK(2 * U <= h->d.max_seqs, "cv2_flow_inference_chunk: %d utterances exceed max_seqs/2", U);
@@ -1873,17 +1927,17 @@ extern "C" int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, c
     SpkArgs sp{(const float* const*)dp, h->w.spk_w, h->w.spk_b, h->spk};
     hipLaunchKernelGGL(k_spk, dim3(U), dim3(128), 0, s, sp);
     EmbedPtrArgs ea{(const int* const*)(dp + 3 * U), h->w.input_embedding, LA.tab(), LA.rows, GB(h->e_a, 512)};
-    hipLaunchKernelGGL(k_embed_tokens_ptr, dim3((LA.rows + 1) / 2), dim3(256), 0, s, ea);
+    hipLaunchKernelGGL(k_embed_tokens_ptr<OP>, dim3((LA.rows + 1) / 2), dim3(256), 0, s, ea);
     EncInc einc;
     for (int u = 0; enc_cache && u < U; u++) {
         einc.base.push_back((uint16_t*)refs[u].cache + enc_part_off(h, refs[u].cache_frames));
         einc.frames.push_back(refs[u].cache_frames); einc.n0_tok.push_back(refs[u].n_cached / 2); einc.gen.push_back(refs[u].gen);
     }
-    if (encoder_core(h, LA, LT, L2, 1, nullptr, s, enc_cache ? &einc : nullptr)) return -1;
+    if (encoder_core<OP>(h, LA, LT, L2, 1, nullptr, s, enc_cache ? &einc : nullptr)) return -1;
     {
         GemmArgs a = gemm_args(GB(h->e_ln, 512), 512, 0, h->w.enc_proj.w, L2.rows, 128, 512);
         a.bias = h->w.enc_proj.b; a.out_f32 = h->mu; a.ldo = 80; a.n_store = 80; a.seq = L2.tab(); a.mask = 1;
-        if (gemm_launch_cfg(a, 0, 1, true, s)) return -1;
+        if (gemm_launch_cfg<OP>(a, 0, 1, true, s)) return -1;
     }
     // Euler loop over the new frames only
     EstCtx c{h, &LIE, nullptr, 50, s};
@@ -1892,17 +1946,37 @@ extern "C" int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, c
         PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, st == 0 ? h->w.rand_noise : nullptr,
                    st == 0 ? nullptr : h->vf, st == 0 ? 0.f : h->dt_host[st - 1], h->d.cfg_rate, LI.tab(), RI, U, GB(h->a0, 320),
                    ibase + 3 * U, ibase + 2 * U, twin, INC_LEAD};
-        hipLaunchKernelGGL(k_euler_pack, dim3(((long)RI * 20 + 255) / 256), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k_euler_pack<OP>, dim3(((long)RI * 20 + 255) / 256), dim3(256), 0, s, p);
         if (st == h->d.n_timesteps) break;                       // last update: no estimator call follows
         c.temb = h->temb_tab + (size_t)st * 14 * 256;
         c.step = st;
-        if (estimator_core(c)) return -1;
+        if (estimator_core<OP>(c)) return -1;
     }
     MelOutArgs mo{h->xs, (float* const*)(dp + 2 * U), ibase + U, LI.tab()};
     hipLaunchKernelGGL(k_mel_out, dim3(((long)maxn2 * 80 + 255) / 256, U), dim3(256), 0, s, mo);
     CV2_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------ C entry points: one body per entry, instantiated for both operand
+// formats; the engine's cv2_flow_dims.operands (fixed at cv2_flow_create) picks the instantiation.  (A null handle takes the bf16 one,
+// whose argument check reports it.)
+#define FLOW_OPS(fn, h, ...) ((h) && (h)->d.operands == CV2_OPERANDS_FP16 ? fn<OpF16>(h, __VA_ARGS__) : fn<OpBF16>(h, __VA_ARGS__))
+extern "C" int cv2_flow_estimator(cv2_flow* h, float* x, const float* mask, const float* mu, const float* t, const float* spks,
+                                  const float* cond, int32_t T, int32_t streaming, void* stream) {
+    return FLOW_OPS(cv2_flow_estimator_t, h, x, mask, mu, t, spks, cond, T, streaming, stream);
+}
+extern "C" int cv2_flow_encoder(cv2_flow* h, const float* xs, int32_t T, const float* context, int32_t streaming, float* out, void* stream) {
+    return FLOW_OPS(cv2_flow_encoder_t, h, xs, T, context, streaming, out, stream);
+}
+extern "C" int cv2_flow_inference(cv2_flow* h, const cv2_flow_utt* utts, int32_t U, int32_t streaming, int32_t finalize, void* stream) {
+    return FLOW_OPS(cv2_flow_inference_t, h, utts, U, streaming, finalize, stream);
+}
+extern "C" int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, int32_t U, int32_t finalize,
+                                        void* stream) {
+    return FLOW_OPS(cv2_flow_inference_chunk_t, h, utts, refs, U, finalize, stream);
+}
+#undef FLOW_OPS
 
 // ------------------------------------------------------------------ test hook: the epilogue activations as the GEMM kernels evaluate them
 __global__ void k_dbg_act(const float* x, float* out, int n, int act, float slope) {

@@ -14,6 +14,9 @@
 // stages) and finished row-wise: bias, LayerNorm over the row, activation, per-sequence vector add, sequence
 // mask, fp32 residual, fp32 / bf16 stores, a second LayerNorm for the next GEMM's operand, or a transposed
 // bf16 store (V^T for attention).  Rows live in the packed ragged layout described in flow.hip.
+// Operand format: every kernel below takes the 16-bit format of its operands as a trait (OP, common.h): OpBF16 (the default, the LLM
+// prefill and a bf16 flow engine) or OpF16 (an fp16 flow engine) -- one body, the MFMA and the fp32 -> 16-bit conversions from the trait;
+// "bf16" in the comments below stands for the engine's format.
 #pragma once
 #include "common.h"
 
@@ -146,7 +149,7 @@ __device__ __forceinline__ void xcd_tile(int& bx, int& by) {
 // cache append -- the estimator's QKV projection): the general epilogue below is ~1 000 executed instructions per wave and tile with all
 // its run-time switches (phase stamps at 32 utterances: 7 560 of a block's 17 600 cycles for the 128 x 128 x 256 QKV tile); this one is
 // 8 x {LDS read, two conversions, store}.
-template <int BM, int BN, int WM, int WN, bool WPACKED, bool SPLITA = false, int NSTAGE = 2, int EPI = 0>
+template <int BM, int BN, int WM, int WN, bool WPACKED, bool SPLITA = false, int NSTAGE = 2, int EPI = 0, class OP = OpBF16>
 __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
     constexpr int NW = WM * WN, NT_ = NW * 64;
     constexpr int TM = BM / WM, TN = BN / WN, MT = TM / 16, NT = TN / 16;
@@ -265,21 +268,21 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
         const char* base = smem + buf * STAGE;
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) {
-            bf16x8 af[MT], al[SPLITA ? MT : 1], wf[NT];
+            v8_t<OP> af[MT], al[SPLITA ? MT : 1], wf[NT];
 #pragma unroll
             for (int i = 0; i < MT; i++) {
-                af[i] = *reinterpret_cast<const bf16x8*>(base + ((wm * MT + i) * 2 + ks) * 1024 + a_off);
-                if (SPLITA) al[i] = *reinterpret_cast<const bf16x8*>(base + (NA + (wm * MT + i) * 2 + ks) * 1024 + a_off);
+                af[i] = *reinterpret_cast<const v8_t<OP>*>(base + ((wm * MT + i) * 2 + ks) * 1024 + a_off);
+                if (SPLITA) al[i] = *reinterpret_cast<const v8_t<OP>*>(base + (NA + (wm * MT + i) * 2 + ks) * 1024 + a_off);
             }
 #pragma unroll
             for (int j = 0; j < NT; j++)
-                wf[j] = *reinterpret_cast<const bf16x8*>(base + (NAP + (wn * NT + j) * 2 + ks) * 1024 + w_off);
+                wf[j] = *reinterpret_cast<const v8_t<OP>*>(base + (NAP + (wn * NT + j) * 2 + ks) * 1024 + w_off);
 #pragma unroll
             for (int j = 0; j < NT; j++)
 #pragma unroll
                 for (int i = 0; i < MT; i++) {
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[j][i], 0, 0, 0);
-                    if (SPLITA) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], al[i], acc[j][i], 0, 0, 0);
+                    acc[j][i] = OP::mfma16(wf[j], af[i], acc[j][i]);
+                    if (SPLITA) acc[j][i] = OP::mfma16(wf[j], al[i], acc[j][i]);
                 }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -324,7 +327,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
                     if (s < 0 || mrow + 2 * r - start >= len) v0 = 0.f;
                     if (s < 0 || mrow + 2 * r + 1 - start >= len) v1 = 0.f;
                 }
-                pk[r] = pack_bf16x2(v0, v1);
+                pk[r] = OP::pack2(v0, v1);
             }
             *reinterpret_cast<uint4*>(a.vt + (size_t)(n0 + n - a.vt_n0) * a.vt_ld + mrow) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             if (a.kvc && s >= 0) {                         // the same 8 frames of this feature -> the sequence's V^T cache (pos0 and t are even: 4-byte pairs)
@@ -350,7 +353,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
             const bool valid = !a.mask || (m0 + ml - ep_start[BM > 64 ? tl : 0]) < ep_len[BM > 64 ? tl : 0];
             f32x4 v = *reinterpret_cast<const f32x4*>(&C[ml * LDC + cl * 4]);
             if (!valid) v = z4;
-            if (wr) *reinterpret_cast<uint2*>(out_bf16 + (size_t)(m0 + ml) * a.ldo16 + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            if (wr) *reinterpret_cast<uint2*>(out_bf16 + (size_t)(m0 + ml) * a.ldo16 + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         }
         SK_STAMP(5);
         SK_STAMP_FLUSH_RING(((unsigned long long)a.K << 32) | (unsigned)a.N,
@@ -387,12 +390,12 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
         const bool wr = n < a.n_store;
         if (out_f32 && wr) *reinterpret_cast<f32x4*>(out_f32 + (size_t)m * a.ldo + n) = v;
         if (out_bf16 && wr)
-            *reinterpret_cast<uint2*>(out_bf16 + (size_t)m * a.ldo16 + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(out_bf16 + (size_t)m * a.ldo16 + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         if (a.kvc && n >= a.kvc_k0 && wr && valid && a.seq.tile_seq) {       // this row's key channels -> the sequence's K cache
             const int s = a.seq.tile_seq[m >> 6];
             const long fr = a.kvc_frames[s];
             uint16_t* d = a.kvc[s] + a.kvc_slot * fr * 1024 + (size_t)(a.kvc_pos0[s] + m - a.seq.seq_start[s]) * 512 + (n - a.kvc_k0);
-            *reinterpret_cast<uint2*>(d) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(d) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         }
         if (a.ln2_g) {
             const float mean = group_sum<LPR>(v[0] + v[1] + v[2] + v[3]) * (1.f / BN);
@@ -401,7 +404,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
             const float rstd = rsqrtf(var + a.ln2_eps);
             f32x4 y = (d * rstd * ep_g2 + ep_b2) * a.ln2_scale;
             if (a.mask && !valid) y = (f32x4){0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<uint2*>(a.out_ln2 + (size_t)m * a.ldo_ln2 + n) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+            *reinterpret_cast<uint2*>(a.out_ln2 + (size_t)m * a.ldo_ln2 + n) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
         }
     }
     SK_STAMP(5);                                         // row epilogue done
@@ -420,7 +423,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs a) {
 // Same arguments and epilogue semantics as k_gemm (no transposed-V path, packed weights, K % (32 CH) == 0).
 // KS_T = K / 32 at compile time: the K loop is straight-line code, so the waits hipcc derives for the ring are exact counted
 // ones (around a run-time loop it falls back to vmcnt(0) at the loop head, which serialises load and use chunk by chunk).
-template <int CH, int KS_T>
+template <int CH, int KS_T, class OP = OpBF16>
 __global__ __launch_bounds__(1024) void k_gemm_panel(GemmArgs a) {
     constexpr int BM = 16, BN = 256, NW = 16, LDC = BN + 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -480,8 +483,8 @@ __global__ __launch_bounds__(1024) void k_gemm_panel(GemmArgs a) {
     f32x4 acc = z4;
 #pragma unroll
     for (int kb = 0; kb < KS; kb++) {
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(ap + (size_t)kb * 1024);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wr[kb % CH]), af, acc, 0, 0, 0);
+        const v8_t<OP> af = *reinterpret_cast<const v8_t<OP>*>(ap + (size_t)kb * 1024);
+        acc = OP::mfma16(__builtin_bit_cast(v8_t<OP>, wr[kb % CH]), af, acc);
         if (kb + CH < KS) wr[kb % CH] = wp[(size_t)(kb + CH) * 64];
     }
     SK_STAMP(3);                                         // K loop done
@@ -517,7 +520,7 @@ __global__ __launch_bounds__(1024) void k_gemm_panel(GemmArgs a) {
         uint16_t* out_bf16 = a.out_bf16 ? a.out_bf16 + (size_t)blockIdx.z * a.o16_bstride : nullptr;
         if (out_f32 && wr) *reinterpret_cast<f32x4*>(out_f32 + (size_t)m * a.ldo + n) = v;
         if (out_bf16 && wr)
-            *reinterpret_cast<uint2*>(out_bf16 + (size_t)m * a.ldo16 + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(out_bf16 + (size_t)m * a.ldo16 + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         if (a.ln2_g) {
             const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / BN);
             const f32x4 d = v - mean;
@@ -525,7 +528,7 @@ __global__ __launch_bounds__(1024) void k_gemm_panel(GemmArgs a) {
             const float rstd = rsqrtf(var + a.ln2_eps);
             f32x4 y = (d * rstd * ep_g2 + ep_b2) * a.ln2_scale;
             if (a.mask && !valid) y = z4;
-            *reinterpret_cast<uint2*>(a.out_ln2 + (size_t)m * a.ldo_ln2 + n) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+            *reinterpret_cast<uint2*>(a.out_ln2 + (size_t)m * a.ldo_ln2 + n) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
         }
     }
     SK_STAMP(5);
@@ -567,7 +570,7 @@ struct TailArgs {
 // Everything up to norm3 is repeated by every part (W_o: 256 KB); the S partial FF2 tiles meet in the panel's last-arriving workgroup
 // (write-through partials, arrival counter, sc1 loads; cdna_hip_programming.md Guideline 16), which sums them in part order -- the
 // result does not depend on who arrives last -- and runs the row epilogue.  grid = (S, panels).
-template <int S>
+template <int S, class OP = OpBF16>
 __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
     constexpr int NW = 16, LDC = 260, KS0 = 16, KS1 = 8, KS2 = 32, CH = 8;
     constexpr size_t ATT_BYTES = (size_t)KS0 * 1024, X_OFF = 17 * 1024, H_OFF = X_OFF + KS1 * 1024, PAR_OFF = H_OFF + KS2 * 1024;
@@ -616,8 +619,8 @@ __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
     f32x4 acc = z4;
 #pragma unroll
     for (int kb = 0; kb < KS0; kb++) {
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(smem + (size_t)kb * 1024 + a_off);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wr[kb % CH]), af, acc, 0, 0, 0);
+        const v8_t<OP> af = *reinterpret_cast<const v8_t<OP>*>(smem + (size_t)kb * 1024 + a_off);
+        acc = OP::mfma16(__builtin_bit_cast(v8_t<OP>, wr[kb % CH]), af, acc);
         if (kb + CH < KS0) wr[kb % CH] = wop[(size_t)(kb + CH) * 64];
     }
     // first fragments of W1 requested now: they fly during the epilogue below
@@ -638,7 +641,7 @@ __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
         f32x4 y = d * rsqrtf(var + a.eps3) * pv[64] + pv[128];
         if (!valid) y = z4;
         char* dst = xs + (size_t)(n >> 5) * 1024 + subtile_off(wave, (n & 31) >> 3) + (n & 7) * 2;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+        *reinterpret_cast<uint2*>(dst) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
     }
     __syncthreads();
     // ---- GEMM 1: 4 column tiles of 16 hidden columns per wave, bias + GELU, hidden panel in operand layout
@@ -653,15 +656,15 @@ __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
         f32x4 a1 = z4;
 #pragma unroll
         for (int kb = 0; kb < KS1; kb++) {
-            const bf16x8 xf_ = *reinterpret_cast<const bf16x8*>(xs + (size_t)kb * 1024 + a_off);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cur[kb]), xf_, a1, 0, 0, 0);
+            const v8_t<OP> xf_ = *reinterpret_cast<const v8_t<OP>*>(xs + (size_t)kb * 1024 + a_off);
+            a1 = OP::mfma16(__builtin_bit_cast(v8_t<OP>, cur[kb]), xf_, a1);
         }
         const int c = wave * (16 * TPW) + t * 16 + 4 * (lane >> 4);        // hidden column within the part
         f32x4 v = a1 + *reinterpret_cast<const f32x4*>(a.b1 + part * (1024 / S) + c);
 #pragma unroll
         for (int e = 0; e < 4; e++) v[e] = act_apply(v[e], ACT_GELU, 0.f);
         char* d = hs + (size_t)(c >> 5) * 1024 + subtile_off(lane & 15, (c & 31) >> 3) + (c & 7) * 2;
-        *reinterpret_cast<uint2*>(d) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+        *reinterpret_cast<uint2*>(d) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
     }
     // ---- GEMM 2
     const s16x8* w2p = reinterpret_cast<const s16x8*>(a.W2) + ((size_t)wave * KS2 + part * KS2P) * 64 + lane;
@@ -676,8 +679,8 @@ __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
     for (int c8 = 0; c8 < KS2P / 8; c8++) q2[c8] = z4;
 #pragma unroll
     for (int kb = 0; kb < KS2P; kb++) {
-        const bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (size_t)kb * 1024 + a_off);
-        q2[kb / 8] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wr[kb % CH]), hf, q2[kb / 8], 0, 0, 0);
+        const v8_t<OP> hf = *reinterpret_cast<const v8_t<OP>*>(hs + (size_t)kb * 1024 + a_off);
+        q2[kb / 8] = OP::mfma16(__builtin_bit_cast(v8_t<OP>, wr[kb % CH]), hf, q2[kb / 8]);
         if (kb + CH < KS2P) wr[kb % CH] = w2p[(size_t)(kb + CH) * 64];
     }
     f32x4 acc2;
@@ -719,9 +722,9 @@ __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
             const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 256);
             f32x4 y = d * rsqrtf(var + a.epsn) * pv[256] + pv[320];
             if (!valid) y = z4;
-            *reinterpret_cast<uint2*>(a.out_ln + (size_t)m * a.ldo_ln + n) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+            *reinterpret_cast<uint2*>(a.out_ln + (size_t)m * a.ldo_ln + n) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
         } else {
-            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         }
     }
 }
@@ -734,7 +737,7 @@ constexpr size_t tail_panel_smem() { return (size_t)(17 + 8 + 32 + 6) * 1024; }
 // consumed in four quarters of 256 columns (LDS: attention panel 16 RT KiB | x panel 8 RT | hidden quarter 8 RT), the FF2
 // accumulators stay in registers across the quarters.  Wave w owns output columns [16 w, 16 w + 16) of the N = 256 GEMMs and hidden
 // columns [16 w, 16 w + 16) of each quarter; rows: wave w finishes rows w, w + 16, ... (tile i, row w) in the row epilogues.
-template <int RT>
+template <int RT, class OP = OpBF16>
 __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
     constexpr int LDC = 260, KS0 = 16, KS1 = 8, KS2 = 32, CH = 8, QK = 8;      // QK = k-steps of one hidden quarter
     constexpr size_t C_BYTES = (size_t)RT * 16 * LDC * 4, ATT_BYTES = (size_t)KS0 * RT * 1024;
@@ -789,11 +792,11 @@ __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
     for (int rt = 0; rt < RT; rt++) acc[rt] = z4;
 #pragma unroll
     for (int kb = 0; kb < KS0; kb++) {
-        const bf16x8 wf = __builtin_bit_cast(bf16x8, wr[kb % CH]);
+        const v8_t<OP> wf = __builtin_bit_cast(v8_t<OP>, wr[kb % CH]);
 #pragma unroll
         for (int rt = 0; rt < RT; rt++) {
-            const bf16x8 af = *reinterpret_cast<const bf16x8*>(smem + (size_t)(kb * RT + rt) * 1024 + a_off);
-            acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, af, acc[rt], 0, 0, 0);
+            const v8_t<OP> af = *reinterpret_cast<const v8_t<OP>*>(smem + (size_t)(kb * RT + rt) * 1024 + a_off);
+            acc[rt] = OP::mfma16(wf, af, acc[rt]);
         }
         if (kb + CH < KS0) wr[kb % CH] = wop[(size_t)(kb + CH) * 64];
     }
@@ -820,7 +823,7 @@ __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
         f32x4 y = d * rsqrtf(var + a.eps3) * pv[64] + pv[128];
         if (!valid) y = z4;
         char* dst = xs + (size_t)((n >> 5) * RT + i) * 1024 + subtile_off(wave, (n & 31) >> 3) + (n & 7) * 2;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+        *reinterpret_cast<uint2*>(dst) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
     }
     __syncthreads();
     // ---- feed-forward, one hidden quarter at a time; FF2 accumulates over the quarters
@@ -834,11 +837,11 @@ __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
         for (int rt = 0; rt < RT; rt++) a1[rt] = z4;
 #pragma unroll
         for (int kb = 0; kb < KS1; kb++) {
-            const bf16x8 wf = __builtin_bit_cast(bf16x8, w1[kb]);
+            const v8_t<OP> wf = __builtin_bit_cast(v8_t<OP>, w1[kb]);
 #pragma unroll
             for (int rt = 0; rt < RT; rt++) {
-                const bf16x8 xf_ = *reinterpret_cast<const bf16x8*>(xs + (size_t)(kb * RT + rt) * 1024 + a_off);
-                a1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf_, a1[rt], 0, 0, 0);
+                const v8_t<OP> xf_ = *reinterpret_cast<const v8_t<OP>*>(xs + (size_t)(kb * RT + rt) * 1024 + a_off);
+                a1[rt] = OP::mfma16(wf, xf_, a1[rt]);
             }
         }
         {   // this quarter's W2 fragments (k-steps 8 hq .. 8 hq + 7 of output tile `wave`), then the next quarter's W1
@@ -854,7 +857,7 @@ __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; e++) v[e] = act_apply(v[e], ACT_GELU, 0.f);
             char* d = hs + (size_t)((cq >> 5) * RT + rt) * 1024 + subtile_off(lane & 15, (cq & 31) >> 3) + (cq & 7) * 2;
-            *reinterpret_cast<uint2*>(d) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(d) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         }
         if (hq + 1 < 4) {
             const s16x8* w1p = reinterpret_cast<const s16x8*>(a.W1) + ((size_t)((hq + 1) * 16 + wave) * KS1) * 64 + lane;
@@ -864,11 +867,11 @@ __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
         __syncthreads();                                     // hidden quarter complete
 #pragma unroll
         for (int kb = 0; kb < QK; kb++) {
-            const bf16x8 wf = __builtin_bit_cast(bf16x8, w2[kb]);
+            const v8_t<OP> wf = __builtin_bit_cast(v8_t<OP>, w2[kb]);
 #pragma unroll
             for (int rt = 0; rt < RT; rt++) {
-                const bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (size_t)(kb * RT + rt) * 1024 + a_off);
-                acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, hf, acc[rt], 0, 0, 0);
+                const v8_t<OP> hf = *reinterpret_cast<const v8_t<OP>*>(hs + (size_t)(kb * RT + rt) * 1024 + a_off);
+                acc[rt] = OP::mfma16(wf, hf, acc[rt]);
             }
         }
         __syncthreads();                                     // hidden panel consumed: the next quarter may overwrite it
@@ -889,9 +892,9 @@ __global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
             const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 256);
             f32x4 y = d * rsqrtf(var + a.epsn) * pv[256] + pv[320];
             if (!valid) y = z4;
-            *reinterpret_cast<uint2*>(a.out_ln + (size_t)m * a.ldo_ln + n) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+            *reinterpret_cast<uint2*>(a.out_ln + (size_t)m * a.ldo_ln + n) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
         } else {
-            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         }
     }
 }
@@ -932,15 +935,15 @@ struct Tr2NoHook { __device__ __forceinline__ void operator()(int) const {} };
 // SWAP: the activation fragment is the MFMA's first operand and the weight fragment its second -- the same products summed over k in the same
 // order (bit-identical values), but the accumulator tile comes out TRANSPOSED: a lane then holds four consecutive ROWS of one column (the
 // chained V projection stages its tile as V^T with 8-byte writes instead of gathering 2-byte elements, k_tail_rows2)
-template <int NKS, int NNKS, int PH, class SIDE = Tr2NoHook, bool SWAP = false>
+template <class OP, int NKS, int NNKS, int PH, class SIDE = Tr2NoHook, bool SWAP = false>
 __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x8* w1, const s16x8* nw0, const s16x8* nw1,
                                          const char* panel, int a_off, unsigned lane16, f32x4 (&acc)[2][4], SIDE side = SIDE()) {
     // software pipeline, fenced per k-step (left to itself hipcc hoists the fully unrolled loop's LDS reads and weight loads far ahead:
     // 256 VGPRs + 370 spilled): the NEXT k-step's four activation fragments and this slot's refill are requested, then this k-step's
     // eight MFMAs run
-    bf16x8 af[2][4];
+    v8_t<OP> af[2][4];
 #pragma unroll
-    for (int rt = 0; rt < 4; rt++) af[0][rt] = *reinterpret_cast<const bf16x8*>(panel + (size_t)rt * 1024 + a_off);
+    for (int rt = 0; rt < 4; rt++) af[0][rt] = *reinterpret_cast<const v8_t<OP>*>(panel + (size_t)rt * 1024 + a_off);
 #ifdef TR2_DIAG_MFMA32
     // TIMING-ONLY diagnostic (round 6, the round-5 review's item 4a; results are numerically meaningless): the k-step's eight
     // v_mfma_f32_16x16x32_bf16 (each holds the SIMD's vector issue 8 of its 16 cycles) replaced by four v_mfma_f32_32x32x16_bf16 (8 of 32)
@@ -953,17 +956,17 @@ __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x
 #pragma unroll
     for (int kb = 0; kb < NKS; kb++) {
         const int sl = (PH + kb) % TR2_CH;
-        const bf16x8 f0 = __builtin_bit_cast(bf16x8, R.r0[sl]), f1 = __builtin_bit_cast(bf16x8, R.r1[sl]);
+        const v8_t<OP> f0 = __builtin_bit_cast(v8_t<OP>, R.r0[sl]), f1 = __builtin_bit_cast(v8_t<OP>, R.r1[sl]);
         if (kb + 1 < NKS) {
 #pragma unroll
-            for (int rt = 0; rt < 4; rt++) af[(kb + 1) & 1][rt] = *reinterpret_cast<const bf16x8*>(panel + (size_t)((kb + 1) * 4 + rt) * 1024 + a_off);
+            for (int rt = 0; rt < 4; rt++) af[(kb + 1) & 1][rt] = *reinterpret_cast<const v8_t<OP>*>(panel + (size_t)((kb + 1) * 4 + rt) * 1024 + a_off);
         }
         __builtin_amdgcn_sched_barrier(0);
 #ifdef TR2_DIAG_MFMA32
-        t32a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f0, af[kb & 1][0], t32a, 0, 0, 0);
-        t32b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f1, af[kb & 1][1], t32b, 0, 0, 0);
-        t32a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f0, af[kb & 1][2], t32a, 0, 0, 0);
-        t32b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f1, af[kb & 1][3], t32b, 0, 0, 0);
+        t32a = OP::mfma32(f0, af[kb & 1][0], t32a);
+        t32b = OP::mfma32(f1, af[kb & 1][1], t32b);
+        t32a = OP::mfma32(f0, af[kb & 1][2], t32a);
+        t32b = OP::mfma32(f1, af[kb & 1][3], t32b);
         side(kb);
         asm volatile("" : "+v"(t32a), "+v"(t32b));
         if (kb + TR2_CH < NKS) { R.r0[sl] = tr2_ld(w0, kb + TR2_CH, lane16); R.r1[sl] = tr2_ld(w1, kb + TR2_CH, lane16); }
@@ -974,10 +977,10 @@ __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x
 #pragma unroll
         for (int rt = 0; rt < 4; rt++) {
 #ifndef TR2_DIAG_NOMFMA
-            acc[0][rt] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kb & 1][rt], f0, acc[0][rt], 0, 0, 0)
-                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(f0, af[kb & 1][rt], acc[0][rt], 0, 0, 0);
-            acc[1][rt] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kb & 1][rt], f1, acc[1][rt], 0, 0, 0)
-                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1, af[kb & 1][rt], acc[1][rt], 0, 0, 0);
+            acc[0][rt] = SWAP ? OP::mfma16(af[kb & 1][rt], f0, acc[0][rt])
+                              : OP::mfma16(f0, af[kb & 1][rt], acc[0][rt]);
+            acc[1][rt] = SWAP ? OP::mfma16(af[kb & 1][rt], f1, acc[1][rt])
+                              : OP::mfma16(f1, af[kb & 1][rt], acc[1][rt]);
 #else
             acc[0][rt] += __builtin_bit_cast(f32x4, f0) + __builtin_bit_cast(f32x4, af[kb & 1][rt]);
             acc[1][rt] += __builtin_bit_cast(f32x4, f1);
@@ -997,7 +1000,7 @@ __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x
     for (int i = 0; i < 16; i++) { acc[0][i >> 2][i & 3] = t32a[i]; acc[1][i >> 2][i & 3] = t32b[i]; }
 #endif
 }
-template <bool QKV>
+template <bool QKV, class OP = OpBF16>
 __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     constexpr int RT = 4, LDC = 260, KS0 = 16, KS1 = 8, KS2 = 32;
     constexpr size_t P_BYTES = 68 * 1024, X_OFF = P_BYTES, PAR_OFF = X_OFF + 32 * 1024;     // P: attention panel 64 K | C tile 65 K | hidden quarters 2 x 32 K | QKV staging 2 x 33 K
@@ -1072,7 +1075,7 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     // ---- GEMM 0: O projection (ring phase 0; followed by FF1 quarter 0)
     f32x4 acc[2][4], acc2[2][4];
     zero(acc);
-    tr2_gemm<KS0, KS1, 0>(R, wo0, wo1, w1p(0, 0), w1p(0, 1), smem, a_off, lane16, acc);
+    tr2_gemm<OP, KS0, KS1, 0>(R, wo0, wo1, w1p(0, 0), w1p(0, 1), smem, a_off, lane16, acc);
     SK_STAMP(2);                                             // O projection's MFMAs issued
     TR2_BARRIER;                                         // attention panel fully read: its LDS becomes the C tile
     to_c(acc);
@@ -1090,7 +1093,7 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
         f32x4 y = d * rsqrtf(var + a.eps3) * pv[64] + pv[128];
         if (!valid) y = z4;
         char* dst = xs + (size_t)((n >> 5) * RT + (r >> 4)) * 1024 + subtile_off(r & 15, (n & 31) >> 3) + (n & 7) * 2;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+        *reinterpret_cast<uint2*>(dst) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
     }
     TR2_BARRIER;                                         // x panel complete; the C tile is consumed: its LDS becomes the hidden quarters
     // ---- feed-forward, one hidden quarter at a time; FF2 accumulates over the quarters (in order: the sums are k_tail_rows<4>'s).  The
@@ -1109,7 +1112,7 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
         for (int e = 0; e < 4; e++) v[e] = act_apply(v[e], ACT_GELU, 0.f);
 #endif
         char* d = hs + (size_t)((cq >> 5) * RT + rt) * 1024 + subtile_off(lane & 15, (cq & 31) >> 3) + (cq & 7) * 2;
-        *reinterpret_cast<uint2*>(d) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+        *reinterpret_cast<uint2*>(d) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
     };
     auto load_b1 = [&](int hq) {
 #pragma unroll
@@ -1117,7 +1120,7 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     };
     load_b1(0);
     zero(acc);
-    tr2_gemm<KS1, KS1, 0>(R, w1p(0, 0), w1p(0, 1), w1p(1, 0), w1p(1, 1), xs, a_off, lane16, acc);
+    tr2_gemm<OP, KS1, KS1, 0>(R, w1p(0, 0), w1p(0, 1), w1p(1, 0), w1p(1, 1), xs, a_off, lane16, acc);
 #pragma unroll
     for (int t = 0; t < 8; t++) gelu_tile(0, t >> 2, t & 3);
     TR2_BARRIER;                                             // hidden quarter 0 complete
@@ -1125,8 +1128,8 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     {                                                                                                                               \
         load_b1(HQ);                                                                                                                 \
         zero(acc);                                                                                                                   \
-        tr2_gemm<KS1, KS1, 0>(R, w1p(HQ, 0), w1p(HQ, 1), w2p((HQ) - 1, 0), w2p((HQ) - 1, 1), xs, a_off, lane16, acc);                  \
-        tr2_gemm<KS1, NNKS, 0>(R, w2p((HQ) - 1, 0), w2p((HQ) - 1, 1), NW0, NW1, smem + (size_t)(((HQ) - 1) & 1) * 32 * 1024, a_off, lane16, acc2, \
+        tr2_gemm<OP, KS1, KS1, 0>(R, w1p(HQ, 0), w1p(HQ, 1), w2p((HQ) - 1, 0), w2p((HQ) - 1, 1), xs, a_off, lane16, acc);                  \
+        tr2_gemm<OP, KS1, NNKS, 0>(R, w2p((HQ) - 1, 0), w2p((HQ) - 1, 1), NW0, NW1, smem + (size_t)(((HQ) - 1) & 1) * 32 * 1024, a_off, lane16, acc2, \
                                [&](int kb) { gelu_tile(HQ, kb >> 2, kb & 3); });                                                      \
         TR2_BARRIER;                                         /* hidden quarter HQ complete, quarter HQ - 1 consumed */              \
     }
@@ -1134,8 +1137,8 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     TR2_STEP(2, w1p(3, 0), w1p(3, 1), KS1)
     TR2_STEP(3, w2p(3, 0), w2p(3, 1), KS1)
 #undef TR2_STEP
-    if (QKV) tr2_gemm<KS1, KS1, 0>(R, w2p(3, 0), w2p(3, 1), wqp(0, 0), wqp(0, 1), smem + 32 * 1024, a_off, lane16, acc2);
-    else tr2_gemm<KS1, 0, 0>(R, w2p(3, 0), w2p(3, 1), (const s16x8*)nullptr, (const s16x8*)nullptr, smem + 32 * 1024, a_off, lane16, acc2);
+    if (QKV) tr2_gemm<OP, KS1, KS1, 0>(R, w2p(3, 0), w2p(3, 1), wqp(0, 0), wqp(0, 1), smem + 32 * 1024, a_off, lane16, acc2);
+    else tr2_gemm<OP, KS1, 0, 0>(R, w2p(3, 0), w2p(3, 1), (const s16x8*)nullptr, (const s16x8*)nullptr, smem + 32 * 1024, a_off, lane16, acc2);
     SK_STAMP(4);                                             // feed-forward quarters done
     TR2_BARRIER;                                         // the last hidden quarter is consumed: the LDS becomes the C tile again
     to_c(acc2);
@@ -1153,11 +1156,11 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
             const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 256);
             f32x4 y = d * rsqrtf(var + a.epsn) * pv[256] + pv[320];
             if (!valid) y = z4;
-            const uint2 yb = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+            const uint2 yb = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
             if (QKV) *reinterpret_cast<uint2*>(xs + (size_t)((n >> 5) * RT + (r >> 4)) * 1024 + subtile_off(r & 15, (n & 31) >> 3) + (n & 7) * 2) = yb;
             else *reinterpret_cast<uint2*>(a.out_ln + (size_t)m * a.ldo_ln + n) = yb;
         } else {
-            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
         }
     }
     if (!QKV) {
@@ -1172,14 +1175,14 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     {                                                                                                                               \
         uint16_t* S = reinterpret_cast<uint16_t*>(smem + (size_t)((J) & 1) * 34 * 1024);                                              \
         zero(acc);                                                                                                                   \
-        tr2_gemm<KS1, NNKS, 0>(R, wqp(J, 0), wqp(J, 1), NW0, NW1, xs, a_off, lane16, acc);                                                    \
+        tr2_gemm<OP, KS1, NNKS, 0>(R, wqp(J, 0), wqp(J, 1), NW0, NW1, xs, a_off, lane16, acc);                                                    \
         _Pragma("unroll") for (int c = 0; c < 2; c++)                                                                                \
             _Pragma("unroll") for (int rt = 0; rt < 4; rt++) {                                                                       \
                 const int r = rt * 16 + (lane & 15);                                                                                 \
                 f32x4 v = acc[c][rt];                                                                                                \
                 if ((m0 + r - ep_start) >= ep_len) v = z4;                                                                           \
                 *reinterpret_cast<uint2*>(S + (size_t)r * SLD + wave * 32 + c * 16 + 4 * (lane >> 4)) =                               \
-                    make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));                                                    \
+                    make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));                                                    \
             }                                                                                                                       \
         TR2_BARRIER;                                                                                                             \
         _Pragma("unroll") for (int it = 0; it < 4; it++) {                                              /* 32 threads x 16 B per row */ \
@@ -1187,7 +1190,7 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
             *reinterpret_cast<uint4*>(a.qk + (size_t)(m0 + r) * 1024 + (J) * 256 + ch * 8) = *reinterpret_cast<const uint4*>(S + (size_t)r * SLD + ch * 8); \
         }                                                                                                                           \
     }
-    // V features: the accumulators come out transposed (tr2_gemm<.., SWAP>: a lane holds four consecutive rows of one feature), so the tile is
+    // V features: the accumulators come out transposed (tr2_gemm<OP, .., SWAP>: a lane holds four consecutive rows of one feature), so the tile is
     // staged AS V^T [256 features][TLD] with 8-byte writes and leaves in 16-byte pieces (8 rows of a feature: 8 threads cover the 128 B of a
     // feature's 64 rows).  Staged [64][SLD] like Q / K, every 16-byte piece was eight 2-byte LDS reads a row apart -- all on one bank: the
     // two V tiles cost 12 us of a 207 us launch more than the four Q / K tiles' way of storing.
@@ -1196,14 +1199,14 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
         constexpr int TLD = 68;                              /* bf16 per staged V^T row: 64 + 4 (256 x 68 x 2 B = the 34 KB staging buffer) */ \
         uint16_t* S = reinterpret_cast<uint16_t*>(smem + (size_t)((J) & 1) * 34 * 1024);                                              \
         zero(acc);                                                                                                                   \
-        tr2_gemm<KS1, NNKS, 0, Tr2NoHook, true>(R, wqp(J, 0), wqp(J, 1), NW0, NW1, xs, a_off, lane16, acc);                          \
+        tr2_gemm<OP, KS1, NNKS, 0, Tr2NoHook, true>(R, wqp(J, 0), wqp(J, 1), NW0, NW1, xs, a_off, lane16, acc);                          \
         _Pragma("unroll") for (int c = 0; c < 2; c++)                                                                                \
             _Pragma("unroll") for (int rt = 0; rt < 4; rt++) {                                                                       \
                 const int r0 = rt * 16 + 4 * (lane >> 4);        /* this lane's rows r0 .. r0 + 3 of feature f */                    \
                 const int f = wave * 32 + c * 16 + (lane & 15);                                                                      \
                 f32x4 v = acc[c][rt];                                                                                                \
                 _Pragma("unroll") for (int e = 0; e < 4; e++) if ((m0 + r0 + e - ep_start) >= ep_len) v[e] = 0.f;                     \
-                *reinterpret_cast<uint2*>(S + (size_t)f * TLD + r0) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));  \
+                *reinterpret_cast<uint2*>(S + (size_t)f * TLD + r0) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));  \
             }                                                                                                                       \
         TR2_BARRIER;                                                                                                             \
         _Pragma("unroll") for (int it = 0; it < 4; it++) {                                                                           \

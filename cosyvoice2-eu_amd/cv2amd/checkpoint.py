@@ -102,6 +102,56 @@ def validate(llm_sd, flow_sd, hift_sd):
     return llm_sd, flow_sd, hift_sd
 
 
+FP16_MAX = 65504.0                 # largest finite fp16; the fp16 flow engine saturates to it
+FP16_MIN_SUB = 2.0 ** -24          # smallest fp16 subnormal: nonzero |w| below it rounds to zero (half of it or less, exactly; above half, to 2^-24)
+FLOW_FP32_MATRICES = ('input_embedding.weight', 'spk_embed_affine_layer.weight')     # read by VALU kernels in fp32, not packed
+
+
+def flow_matrix_keys(sd):
+    """The flow tensors an engine packs as 16-bit matrix operands (cv2amd/flow.py): every Linear / Conv1d weight."""
+    return [k for k, v in sd.items() if torch.is_tensor(v) and k.endswith('.weight') and v.dim() >= 2 and k not in FLOW_FP32_MATRICES]
+
+
+def fp16_range(sd):
+    """What fp16 operands (FlowEngine(operands='fp16'), CosyVoice2Model(fp16=True)) do to the flow's matrix weights:
+    {'max_abs', 'max_key', 'n_over' (|w| > 65504: saturated), 'n_flush' (0 < |w| < 2^-24: flush to zero), 'n', 'over_keys', 'flush_keys',
+    'n_meta' (tensors without values, skipped)}."""
+    r = dict(max_abs=0.0, max_key=None, n_over=0, n_flush=0, n=0, over_keys=[], flush_keys=[], n_meta=0)
+    for k in flow_matrix_keys(sd):
+        if sd[k].is_meta:                  # (shape-only stand-ins carry no values)
+            r['n_meta'] += 1
+            continue
+        a = sd[k].detach().float().abs()
+        m = float(a.max()) if a.numel() else 0.0
+        if m > r['max_abs']:
+            r['max_abs'], r['max_key'] = m, k
+        over, flush = int((a > FP16_MAX).sum()), int(((a > 0) & (a < FP16_MIN_SUB)).sum())
+        r['n_over'] += over
+        r['n_flush'] += flush
+        r['n'] += a.numel()
+        if over:
+            r['over_keys'].append(k)
+        if flush:
+            r['flush_keys'].append(k)
+    return r
+
+
+def fp16_report(sd):
+    """Lines of the --verify fp16 range report of a flow state dict."""
+    r = fp16_range(sd)
+    if r['n'] == 0:
+        return ['  fp16 operands (fp16=True): no weight values to range-check ({} tensors without data)'.format(r['n_meta'])]
+    lines = ['  fp16 operands (fp16=True): {} matrix weights, largest |w| {:.4g} ({}); {} above 65504 (saturated), {} nonzero below 2^-24 '
+             '(flush to zero)'.format(r['n'], r['max_abs'], r['max_key'], r['n_over'], r['n_flush'])]
+    for k in r['over_keys']:
+        lines.append('  fp16 OVERFLOW {}'.format(k))
+    if len(r['flush_keys']) <= 8:                # (random-looking weights put a handful below 2^-24 in most matrices: a count then)
+        lines += ['  fp16 flush    {}'.format(k) for k in r['flush_keys']]
+    else:
+        lines.append('  fp16 flush    in {} of the matrices'.format(len(r['flush_keys'])))
+    return lines
+
+
 def verify_dir(model_dir, final=True, out=print):
     """`python -m cv2amd.checkpoint --verify <model_dir>`: the strict key / shape diff of llm.pt, flow.pt, hift.pt (`final=False`:
     the `-original` files of cli/cosyvoice.py:240-265) against the architecture the HIP engines implement, without touching a GPU.
@@ -138,6 +188,9 @@ def verify_dir(model_dir, final=True, out=print):
                 'bias (DESIGN.md section 2) and refuse this checkpoint'.format(len(qkv_bias)))
         elif kind == 'flow' and not (missing or unexpected or mism):
             out('  => strict load holds: q / k / v projections carry no bias, to_out carries one (the reading of SURVEY.md 8(c) is confirmed)')
+        if kind == 'flow':
+            for line in fp16_report(sd):
+                out(line)
         bad += len(missing) + len(unexpected) + len(mism)
     out('OK: the three checkpoints match the architecture key for key, shape for shape' if bad == 0 else '{} problem(s)'.format(bad))
     return bad

@@ -48,7 +48,10 @@ class FlowWeights(C.Structure):
 
 class FlowDims(C.Structure):
     _fields_ = [('max_rows', C.c_int32), ('max_seqs', C.c_int32), ('max_len', C.c_int32), ('n_timesteps', C.c_int32),
-                ('cfg_rate', C.c_float)]
+                ('cfg_rate', C.c_float), ('operands', C.c_int32)]
+
+
+OPERANDS = {'bf16': 0, 'fp16': 1}          # include/cv2_amd.h: CV2_OPERANDS_BF16 / CV2_OPERANDS_FP16
 
 
 class FlowUtt(C.Structure):
@@ -90,6 +93,7 @@ def _bind(lib):
     lib.cv2_flow_encoder.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.cv2_gemm_bf16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_void_p]
+    lib.cv2_gemm_f16.argtypes = lib.cv2_gemm_bf16.argtypes
     lib._flow_bound = True
 
 
@@ -105,8 +109,14 @@ class FlowEngine:
     pre_lookahead_len = 3
     input_frame_rate = 25
 
-    def __init__(self, sd, device='cuda:0', max_utts=1, max_len=2048, n_timesteps=10, cfg_rate=0.7):
-        """sd: state dict in the reference's flow.pt schema."""
+    def __init__(self, sd, device='cuda:0', max_utts=1, max_len=2048, n_timesteps=10, cfg_rate=0.7, operands='bf16'):
+        """sd: state dict in the reference's flow.pt schema.  operands: the 16-bit format of every matrix-product
+        operand, 'bf16' (default) or 'fp16' (round to nearest even, saturated to +-65504; the reference's fp16=True); accumulation, norms,
+        softmax statistics, the residual stream and the Euler state stay fp32 either way."""
+        if operands not in OPERANDS:
+            raise ValueError(f"operands must be 'bf16' or 'fp16', not {operands!r}")
+        self.operands = operands
+        pack = W.pack_f16 if operands == 'fp16' else W.pack_bf16
         self.device = dev = torch.device(device)
         self.lib = L.lib()
         _bind(self.lib)
@@ -121,7 +131,7 @@ class FlowEngine:
             n = w.shape[0]
             if n % pad_to:
                 w = torch.cat([w, w.new_zeros(pad_to - n % pad_to, w.shape[1])], 0)
-            t = W.pack_bf16(w.to(dev))
+            t = pack(w.to(dev))
             keep.append(t)
             return t.data_ptr()
 
@@ -192,7 +202,7 @@ class FlowEngine:
 
         per = (max_len + 8 + 127) // 128 * 128
         self.dims = FlowDims(max_rows=2 * max_utts * per, max_seqs=2 * max_utts, max_len=max_len, n_timesteps=n_timesteps,
-                             cfg_rate=cfg_rate)
+                             cfg_rate=cfg_rate, operands=OPERANDS[operands])
         self.max_utts, self.max_len = max_utts, max_len
         nbytes = self.lib.cv2_flow_workspace_bytes(C.byref(self.dims))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)

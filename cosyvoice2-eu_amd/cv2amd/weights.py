@@ -24,16 +24,31 @@ def round_llm_sd(sd):
     return out
 
 
-def pack_bf16(w):
-    """[N, K] fp32/bf16 -> packed bf16 (uint16 view as int16 tensor) in [N/16][K/32][64 lanes][8] order; N padded to 16."""
+def _pack16(w, dtype):
+    """[N, K] -> 16-bit `dtype` values in [N/16][K/32][64 lanes][8] order (int16 view, flat); N padded to 16 with zeros."""
     n, k = w.shape
     assert k % 32 == 0, 'K must be a multiple of 32'
     npad = (n + 15) // 16 * 16
-    wb = torch.zeros(npad, k, dtype=torch.bfloat16, device=w.device)
-    wb[:n] = w.to(torch.bfloat16)
+    wb = torch.zeros(npad, k, dtype=dtype, device=w.device)
+    wb[:n] = w.to(dtype) if dtype is torch.bfloat16 else f16_round(w).to(dtype)
     # [nt, r(16), ks, h(4), j(8)] -> [nt, ks, h, r, j]
     p = wb.view(npad // 16, 16, k // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
     return p.view(torch.int16).reshape(-1)
+
+
+def pack_bf16(w):
+    """[N, K] fp32/bf16 -> packed bf16 (uint16 view as int16 tensor) in [N/16][K/32][64 lanes][8] order; N padded to 16."""
+    return _pack16(w, torch.bfloat16)
+
+
+def f16_round(w):
+    """fp32 -> the fp16 values an fp16 flow engine multiplies by (round to nearest even, saturated to +-65504), as fp32."""
+    return w.float().clamp(-65504.0, 65504.0).half().float()
+
+
+def pack_f16(w):
+    """pack_bf16's layout with fp16 values (rounded to nearest even, saturated to +-65504): the weights of an fp16 flow engine."""
+    return _pack16(w, torch.float16)
 
 
 def interleave_tiles(a, b):

@@ -25,9 +25,9 @@ extern "C" {
 
 const char* cv2_last_error(void);
 /* ABI revision of the structs and entry points below; bumped whenever a struct's layout or a signature changes (2: cv2_hift_weights gained
- * sd_conv[3] in front of src_rb).  cv2_version() returns the library's; a binding built against another revision must refuse to run
+ * sd_conv[3] in front of src_rb; 3: cv2_flow_dims gained `operands`, cv2_gemm_f16 was added).  cv2_version() returns the library's; a binding built against another revision must refuse to run
  * (cv2amd/lib.py does) -- a stale libcv2amd.so would otherwise misread every pointer behind the changed field without any error. */
-#define CV2_ABI_VERSION 2
+#define CV2_ABI_VERSION 3
 int cv2_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -176,6 +176,9 @@ int cv2_skinny_gemm(const uint16_t* w_packed, const float* bias, const float* x,
  * ---------------------------------------------------------------------------------------------- */
 int cv2_gemm_bf16(const uint16_t* a, int64_t lda, const uint16_t* w_packed, const float* bias, float* out, int64_t ldo,
                   int32_t m, int32_t n, int32_t k, void* stream);
+/* The same on fp16 operands (A and W hold fp16 bit patterns, W in the same packed order): the GEMM of an fp16 flow engine. */
+int cv2_gemm_f16(const uint16_t* a, int64_t lda, const uint16_t* w_packed, const float* bias, float* out, int64_t ldo,
+                 int32_t m, int32_t n, int32_t k, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage 2 — token -> mel (replaces CausalMaskedDiffWithXvec.inference, cosyvoice/flow/flow.py:235-283, and
@@ -183,13 +186,16 @@ int cv2_gemm_bf16(const uint16_t* a, int64_t lda, const uint16_t* w_packed, cons
  * CausalConditionalCFM.forward / solve_euler flow/flow_matching.py:200-225,71-123,
  * CausalConditionalDecoder.forward flow/decoder.py:405-494).
  *
- * Linear / Conv1d weights are bf16 in the packed layout above; a Conv1d weight [C_out][C_in][k] is packed as the
+ * Linear / Conv1d weights are 16-bit in the packed layout above, in the engine's operand format (cv2_flow_dims.operands:
+ * bf16, or fp16 rounded to nearest even and saturated to +-65504); a Conv1d weight [C_out][C_in][k] is packed as the
  * [C_out][k*C_in] matrix with column index tap*C_in + c_in (time-major activations make the tap window contiguous).
- * Biases, LayerNorm parameters, embeddings stay fp32.
+ * Biases, LayerNorm parameters, embeddings stay fp32.  Every matrix-product operand of the engine -- weights, the activations
+ * fed to GEMMs and convolutions, attention q / k / v, softmax probabilities, the stream caches' keys / values -- is held in
+ * that format; accumulation, LayerNorm, softmax statistics, the residual stream, the Euler state and the mel stay fp32.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct cv2_flow cv2_flow;
 
-typedef struct { const uint16_t* w; const float* b; } cv2_lin;      /* packed bf16 weight, fp32 bias (may be NULL) */
+typedef struct { const uint16_t* w; const float* b; } cv2_lin;      /* packed 16-bit weight in the engine's operand format, fp32 bias (may be NULL) */
 typedef struct { const float* g; const float* b; } cv2_ln;
 
 typedef struct {            /* ConformerEncoderLayer (transformer/encoder_layer.py:160-236) */
@@ -247,7 +253,11 @@ typedef struct {
     int32_t max_len;        /* longest single sequence in mel frames */
     int32_t n_timesteps;    /* Euler steps (10) */
     float cfg_rate;         /* inference_cfg_rate (0.7) */
+    int32_t operands;       /* CV2_OPERANDS_BF16 = 0, CV2_OPERANDS_FP16 = 1: the 16-bit format of every matrix operand, fixed at
+                               cv2_flow_create (one engine holds one packed weight set; the weights must be packed in this format) */
 } cv2_flow_dims;
+#define CV2_OPERANDS_BF16 0
+#define CV2_OPERANDS_FP16 1
 
 size_t cv2_flow_workspace_bytes(const cv2_flow_dims* d);
 int cv2_flow_create(const cv2_flow_dims* d, const cv2_flow_weights* w, void* workspace, size_t workspace_bytes,
