@@ -13,6 +13,15 @@ Restates, as plain functions over a state dict in the reference's `llm.pt` key s
     `random_sampling` (cosyvoice/utils/common.py:111-139)
 Pinned against the real reference modules by tests/golden/make_golden.py (golden fixtures in
 tests/golden/llm_*.npz) and tests/test_oracle_vs_reference.py.
+
+Two further modes serve the decode-step logit tests (tests/test_llm_logits_gpu.py, tests/test_llm_oracle_modes_cpu.py); the
+default fp32 behaviour above is untouched by them, bit for bit:
+  * fp64: `qwen2_step` works in the dtype of the state dict it is given (`to_fp64(sd)`); the RoPE table stays the fp32
+    definition (it is the specification the device is fed, cv2amd.weights.rope_tables), cast up afterwards
+  * `split_operands()`: the fp32 oracle rounds the activation operand of every GEMM to hi + lo bf16 planes the way the HIP decode
+    kernels do, and nothing else
+`logit_trace` is the teacher-forced trace both are compared on: raw `llm_decoder` outputs of a prefill's last row and of every
+following step under given ids, the KV cache carried.
 """
 import math
 
@@ -35,6 +44,59 @@ class LLMDims:
         self.inter = sd['llm.model.model.layers.0.mlp.gate_proj.weight'].shape[0]
         self.rope_theta = 1e6
         self.eps = 1e-6
+
+
+# ----------------------------- split-operand model of the HIP decode path -----------------------------------
+SPLIT = {'on': False}
+
+
+class split_operands:
+    """Inside this context the (fp32) oracle rounds what the HIP kernels round, and only that: the ACTIVATION operand of every GEMM
+    goes to the matrix cores as two bf16 planes, hi = bf16(v) and lo = bf16(v - hi), both round-to-nearest-even
+    (csrc/skinny.h:40-44 `split8`; csrc/common.h:86-88), the products accumulate in fp32.  What is split:
+      * QKV, gate/up and the head: v = g . x, the RMSNorm weight times the UN-normalised residual stream; the consumer scales its
+        output by the row's rstd afterwards and adds the bias after that -- the deferred RMSNorm (csrc/chain.h:423-435 operand,
+        :450 rstd, :493 `out *= rs`; csrc/llm.hip:978, 992 for the bias).  The same in the launches of any row count
+        (csrc/skinny.h:307, :398) and the prepared operands of the 17 .. 32-row launches (k_prep).
+      * rows that arrive several at once (a prompt, a bistream text block: cv2_llm_prefill_batch / cv2_llm_extend_batch) are
+        normalised first: v = g . (x rstd) (k_rms_split, csrc/llm.hip:1961-1967)
+      * O projection: v = the normalised attention output (csrc/chain.h:359-360 -> :435; prefill csrc/llm.hip:2168)
+      * down projection: v = SiLU(gate) up (csrc/llm.hip:1039 -> chain.h:435; prefill k_swiglu_split, csrc/llm.hip:2185-2188)
+    What is kept exact and therefore not modelled: the KV cache is fp32 (csrc/llm.hip:1002, 1006), the decode attention works on
+    fp32 scores and values (the matrix-core attention splits q, k and v into three bf16 planes = all 24 mantissa bits), the
+    residual stream, the biases, RoPE (the fp32 table), softmax and SiLU are fp32 arithmetic like the oracle's own.
+    hi + lo carries 16 significand bits: relative operand error <= 2^-17."""
+    def __enter__(self):
+        self.prev, SPLIT['on'] = SPLIT['on'], True
+
+    def __exit__(self, *a):
+        SPLIT['on'] = self.prev
+
+
+def _split(v):
+    hi = v.to(torch.bfloat16).to(v.dtype)
+    return hi + (v - hi).to(torch.bfloat16).to(v.dtype)
+
+
+def _norm_linear(x, g, eps, ws, bs):
+    """RMSNorm(x; g) through the linear maps ws (biases bs) as the HIP path computes them (see split_operands)."""
+    rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    if x.shape[0] == 1:                      # one row = a decode step: planes of g . x, rstd applied by the consumer
+        v, post = _split(g * x), rstd
+    else:                                    # several rows = the batched GEMM path: planes of the normalised value
+        v, post = _split(g * (x * rstd)), None
+    outs = []
+    for w, b in zip(ws, bs):
+        y = F.linear(v, w)
+        if post is not None:
+            y = y * post
+        outs.append(y if b is None else y + b)
+    return outs
+
+
+def to_fp64(sd):
+    """The state dict for the fp64 mode: every floating tensor cast up (bf16-rounded GEMM weights stay the values they are)."""
+    return {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
 
 
 def rmsnorm(x, w, eps):
@@ -62,12 +124,20 @@ def qwen2_step(sd, d, x, cache):
     past = 0 if cache[0] is None else cache[0][0].shape[1]
     pos = torch.arange(past, past + L)
     cos, sin = rope_cos_sin(pos, d.rope_theta, d.head_dim)
+    cos, sin = cos.to(x.dtype), sin.to(x.dtype)          # the table is the fp32 definition in every mode (fp32: no-op)
+    sm_dtype = torch.float64 if x.dtype == torch.float64 else torch.float32
+    split = SPLIT['on']
     for i in range(d.layers):
         p = f'llm.model.model.layers.{i}.'
-        h = rmsnorm(x, sd[p + 'input_layernorm.weight'], d.eps)
-        q = F.linear(h, sd[p + 'self_attn.q_proj.weight'], sd[p + 'self_attn.q_proj.bias']).view(L, d.n_q, 64).transpose(0, 1)
-        k = F.linear(h, sd[p + 'self_attn.k_proj.weight'], sd[p + 'self_attn.k_proj.bias']).view(L, d.n_kv, 64).transpose(0, 1)
-        v = F.linear(h, sd[p + 'self_attn.v_proj.weight'], sd[p + 'self_attn.v_proj.bias']).view(L, d.n_kv, 64).transpose(0, 1)
+        if split:
+            q, k, v = _norm_linear(x, sd[p + 'input_layernorm.weight'], d.eps,
+                                   [sd[p + f'self_attn.{n}_proj.weight'] for n in 'qkv'], [sd[p + f'self_attn.{n}_proj.bias'] for n in 'qkv'])
+        else:
+            h = rmsnorm(x, sd[p + 'input_layernorm.weight'], d.eps)
+            q = F.linear(h, sd[p + 'self_attn.q_proj.weight'], sd[p + 'self_attn.q_proj.bias'])
+            k = F.linear(h, sd[p + 'self_attn.k_proj.weight'], sd[p + 'self_attn.k_proj.bias'])
+            v = F.linear(h, sd[p + 'self_attn.v_proj.weight'], sd[p + 'self_attn.v_proj.bias'])
+        q, k, v = q.view(L, d.n_q, 64).transpose(0, 1), k.view(L, d.n_kv, 64).transpose(0, 1), v.view(L, d.n_kv, 64).transpose(0, 1)
         q = q * cos + rotate_half(q) * sin
         k = k * cos + rotate_half(k) * sin
         if cache[i] is not None:
@@ -81,14 +151,54 @@ def qwen2_step(sd, d, x, cache):
         T = past + L
         causal = torch.arange(T)[None, :] <= (past + torch.arange(L))[:, None]
         s = s.masked_fill(~causal[None], float('-inf'))
-        a = torch.softmax(s, dim=-1, dtype=torch.float32)
+        a = torch.softmax(s, dim=-1, dtype=sm_dtype)
         o = torch.matmul(a, vv).transpose(0, 1).reshape(L, d.n_q * 64)
+        if split:
+            x = x + F.linear(_split(o), sd[p + 'self_attn.o_proj.weight'])
+            g, u = _norm_linear(x, sd[p + 'post_attention_layernorm.weight'], d.eps,
+                                [sd[p + 'mlp.gate_proj.weight'], sd[p + 'mlp.up_proj.weight']], [None, None])
+            x = x + F.linear(_split(F.silu(g) * u), sd[p + 'mlp.down_proj.weight'])
+            continue
         x = x + F.linear(o, sd[p + 'self_attn.o_proj.weight'])
         h = rmsnorm(x, sd[p + 'post_attention_layernorm.weight'], d.eps)
         g = F.linear(h, sd[p + 'mlp.gate_proj.weight'])
         u = F.linear(h, sd[p + 'mlp.up_proj.weight'])
         x = x + F.linear(F.silu(g) * u, sd[p + 'mlp.down_proj.weight'])
+    if split:
+        return x                                         # PRE-norm in this mode: head_logits applies the deferred final norm itself
     return rmsnorm(x, sd['llm.model.model.norm.weight'], d.eps)
+
+
+def head_logits(sd, d, y):
+    """Raw `llm_decoder` outputs (before log-softmax) of ONE row y [hidden] of qwen2_step's result, in the current mode."""
+    if SPLIT['on']:      # y is pre-norm here: planes of g . y, rstd after the GEMV, then the bias (csrc/llm.hip:976-978, chain.h:493)
+        g = sd['llm.model.model.norm.weight']
+        rstd = torch.rsqrt(y.pow(2).mean(-1, keepdim=True) + d.eps)
+        return F.linear(_split(g * y), sd['llm_decoder.weight']) * rstd + sd['llm_decoder.bias']
+    return F.linear(y, sd['llm_decoder.weight'], sd['llm_decoder.bias'])
+
+
+class LogitTrace:
+    """Teacher-forced walk over one sequence with the KV cache carried (cost linear in the rows fed): `feed(rows)` runs the rows
+    [L, hidden] behind what has been fed so far and returns the raw `llm_decoder` outputs [vocab] of the last one;
+    `step(id)` feeds speech_embedding[id].  Works in the dtype of `sd` and in the mode that is active at each call."""
+    def __init__(self, sd):
+        self.sd, self.d = sd, LLMDims(sd)
+        self.cache = [None] * self.d.layers
+
+    def feed(self, rows):
+        y = qwen2_step(self.sd, self.d, rows.to(self.sd['llm.model.model.norm.weight'].dtype), self.cache)
+        return head_logits(self.sd, self.d, y[-1])
+
+    def step(self, tok):
+        return self.feed(self.sd['speech_embedding.weight'][tok:tok + 1])
+
+
+def logit_trace(sd, lm_input, ids):
+    """Raw `llm_decoder` outputs [1 + len(ids), vocab]: row 0 after the prefill of `lm_input` [L0, hidden], row 1 + j after feeding
+    ids[j] -- whatever the network itself would have drawn (teacher forcing)."""
+    t = LogitTrace(sd)
+    return torch.stack([t.feed(lm_input)] + [t.step(int(i)) for i in ids])
 
 
 def build_lm_input(sd, text, prompt_text, prompt_speech_token):
@@ -181,7 +291,7 @@ def inference(sd, text, prompt_text, prompt_speech_token, mode='greedy', uniform
     x = lm_input
     for i in range(max_len):
         y = qwen2_step(sd, d, x, cache)
-        logp = F.linear(y[-1], sd['llm_decoder.weight'], sd['llm_decoder.bias']).log_softmax(dim=-1)
+        logp = head_logits(sd, d, y[-1]).log_softmax(dim=-1)
         if i == 0:
             logp[SPEECH_TOKEN_SIZE] = float('-inf')
         if force_len is not None:
@@ -249,7 +359,7 @@ def inference_bistream(sd, text_chunks, prompt_text, prompt_speech_token, mode='
                     continue
             while True:
                 y = qwen2_step(sd, d, lm_input, cache)
-                logp = F.linear(y[-1], sd['llm_decoder.weight'], sd['llm_decoder.bias']).log_softmax(dim=-1)
+                logp = head_logits(sd, d, y[-1]).log_softmax(dim=-1)
                 if next_fill != -1 and len(out_tokens) == next_fill:
                     top = FILL_TOKEN
                     next_fill += n_speech + 1
@@ -270,7 +380,7 @@ def inference_bistream(sd, text_chunks, prompt_text, prompt_speech_token, mode='
     lm_input = torch.cat([lm_input, text_cache, task], dim=0)           # llm.py:817
     while True:
         y = qwen2_step(sd, d, lm_input, cache)
-        logp = F.linear(y[-1], sd['llm_decoder.weight'], sd['llm_decoder.bias']).log_softmax(dim=-1)
+        logp = head_logits(sd, d, y[-1]).log_softmax(dim=-1)
         top = draw(logp, False)
         out_tokens.append(top)
         if top >= SPEECH_TOKEN_SIZE:
