@@ -41,11 +41,14 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 // (by value on purpose: clang lowers __builtin_bit_cast of a vector ELEMENT lvalue as a load from the vector's address, i.e. element 0)
 __device__ __forceinline__ float u2f(unsigned u) { return __builtin_bit_cast(float, u); }
 
+#define GRAN_ROWS 4                             // rows one chain of blocks serves at most (Gran::errs)
 struct Gran {                 // all granule buffers of the engine behind one buffer descriptor (32-bit byte offsets)
     __amdgpu_buffer_rsrc_t rsrc; u64* base; unsigned epoch;
-    int* err;                 // the error word every wait of the chain re-reads (the chain's first slot)
-    int* err2;                // the slot of a block's second row (k_step2), else == err
-    int* errs[4];             // every slot the block's CHAIN serves (k_step4: up to four rows; else {err, err2, err, err2}): a block that gives up
+    int* err;                 // the error word every wait of the block re-reads: the slot of the row it waits for (the chain's first slot unless a role sets it)
+    int* err2;                // deliberately vestigial: == init()'s slot, nothing sets it, errs[] covers it.  fail() still stores to it because dropping the
+                              // store changes k_step / k_step1 (-32 instructions), which the kernel merge kept instruction for instruction; to be
+                              // removed by a change of its own that re-measures the one-row step
+    int* errs[GRAN_ROWS];     // every slot the block's CHAIN serves (k_step_rows: its NC rows, repeated to fill; else all == err): a block that gives up
                               // flags them all -- its consumers see valid tags on whatever it published and never time out themselves, so a row the
                               // block did not flag would draw from garbage logits and commit (k_sample checks CV2_ST_ERR per slot)
     bool spec;                // several rows per launch: most blocks are dispatched AFTER their operand was published -- sweep once before
@@ -53,9 +56,8 @@ struct Gran {                 // all granule buffers of the engine behind one bu
     __device__ __forceinline__ void init(u64* b, unsigned bytes, unsigned ep, int* e, bool sp = false) {
         rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)b, 0, (int)bytes, 0x00020000);
         base = b; epoch = ep; err = err2 = e; spec = sp;
-        errs[0] = errs[1] = errs[2] = errs[3] = e;
+        for (int i = 0; i < GRAN_ROWS; i++) errs[i] = e;
     }
-    __device__ __forceinline__ void set_err2(int* e2) { err2 = e2; errs[1] = errs[3] = e2; }
     template <class F>
     __device__ __forceinline__ bool try_once(F f) const { return spec && __all(f()); }
     // idx = granule index from the start of the buffer
@@ -88,7 +90,7 @@ struct Gran {                 // all granule buffers of the engine behind one bu
             __hip_atomic_store((__attribute__((address_space(1))) int*)err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store((__attribute__((address_space(1))) int*)err2, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-            for (int i = 0; i < 4; i++) __hip_atomic_store((__attribute__((address_space(1))) int*)errs[i], 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int i = 0; i < GRAN_ROWS; i++) __hip_atomic_store((__attribute__((address_space(1))) int*)errs[i], 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     // a wait gives up when its own time is over OR when any block of the launch has given up (the flag is re-read every 16 polls):
@@ -173,7 +175,7 @@ struct OpFold {
         return v;
     }
     static constexpr int IW = 4;                 // operand columns per thread: 5 vectors x 4 granules in flight per lane
-    // one non-blocking look at the operand (k_step4: several rows' loads in flight together); false: not all there yet
+    // one non-blocking look at the operand (rows_core: two rows' loads in flight together); false: not all there yet
     __device__ __forceinline__ bool attempt(int k, bool active, f32x8& r) const {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         bool ok = true;
@@ -223,8 +225,8 @@ template <int IW_>
 struct OpGran {
     static constexpr int IW = IW_;
     const Gran* G; unsigned g0, sentinel, sstride; int dbg;     // sentinel: one granule of the FIRST producer of this vector
-    int grp = 0;                                                 // k_step2: which half of the block runs this provider (own arming word; `wave` is the wave within the half)
-    bool nobar = false;                                          // k_step2: the caller has cleared the arming words behind a barrier of its own
+    int grp = 0;                                                 // rows_core: the row this provider serves (own arming word; `wave` is the wave within the thread group that runs it)
+    bool nobar = false;                                          // rows_core: the caller has cleared the arming words behind a barrier of its own
     __device__ __forceinline__ void issue(int, int, bool) {}
     __device__ __forceinline__ bool attempt(int k, bool active, f32x8& v) const {
         v = (f32x8){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -280,7 +282,7 @@ struct OpAtt {
     const Gran* G; unsigned ag; int n_kv, rep, cnt; int dbg;      // cnt = live tiles
     const OpFold* fold; int col0;                                  // the block's 16 residual columns, fetched by 16 idle lanes beside the first chunk
     unsigned qg, kvg;                                              // q [n_q * 64] and the new token's key / value rows [2][n_kv][64] of this layer
-    int t0 = 0, grp = 0;                                           // k_step2: first thread of the half that runs this provider, its residual slot
+    int t0 = 0, grp = 0;                                           // rows_core: first thread of the half that runs this provider, its residual slot
     __device__ __forceinline__ void issue(int, int, bool) {}
     __device__ __forceinline__ f32x8 finish(int k, int, int, bool act, char* xch_) {
         const int tid = (int)threadIdx.x - t0;
@@ -496,17 +498,23 @@ __device__ __forceinline__ float row1_core(const uint16_t* __restrict__ W, int t
 }
 
 
-// ---- two rows per block (k_step2): the rows are columns 0 and 1 of the MFMA's B operand, so one pass over the block's weight fragments
-// and one set of MFMAs serve both.  SPLIT (operands of <= 256 items: Q, O, gate/up, head): the two halves of the block fetch and stage
-// the two rows' operands at the same time (op0 by threads 0..255, op1 by 256..511, wave index relative to the half); otherwise (down
-// projection, 304 items) all threads fetch row 0, then row 1.  Returns feature f of row c in thread c * NWR * 16 + f.  Per row the
-// arithmetic (order of every sum) is row1_core's.
-#define R2_STAGE_BYTES(nks) ((nks) * 256)
-__device__ __host__ constexpr int r2_smem_bytes(int nks) { return R2_STAGE_BYTES(nks) + R1_XCH_BYTES + 32 + 2 * 8 * 4 * 16; }
-template <int NWR, int NWK, int MAXKS, bool NORM, bool SPLIT, bool NT, class OP, class HOOK = R1NoHook>
-__device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int tile0, int tstride, int KS, int K, int ks0, int ks1, OP& op0, OP& op1,
+// ---- NC (2 or 4) rows per block (k_step_rows): the rows are columns 0 .. NC - 1 of the MFMA's B operand, so one pass over the block's
+// weight fragments and one set of MFMAs serve them all.  SPLIT (operands of <= 256 items: Q, O, gate/up, head): the two halves of the
+// block fetch and stage their rows' operands at the same time (threads 0..255 and 256..511, wave index relative to the half) -- at two
+// rows one row per half, at four rows 2 h and 2 h + 1 in half h; otherwise (down projection, 304 items) all threads fetch the rows two at
+// a time.  Where two rows go through one thread group their producers publish together: one attempt with both rows' loads in flight (one
+// round trip), the blocking providers one after the other where that fails.  ops[r].grp must be r (own arming word per row, cleared
+// here), OpGran::nobar set.  Returns feature f of row c in thread c * NWR * 16 + f.  Per row the arithmetic (order of every sum) is
+// row1_core's.
+#define ROWS_STAGE_BYTES(NC, nks) ((nks) * (NC) * 128)
+template <int NC>
+__device__ __host__ constexpr int rows_smem_bytes(int nks) { return ROWS_STAGE_BYTES(NC, nks) + R1_XCH_BYTES + NC * 16 + NC * 8 * 4 * 16; }
+template <int NC, int NWR, int NWK, int MAXKS, bool NORM, bool SPLIT, bool NT, class OP, class HOOK = R1NoHook>
+__device__ __forceinline__ float rows_core(const uint16_t* __restrict__ W, int tile0, int tstride, int KS, int K, int ks0, int ks1, OP (&ops)[NC],
                                            const float* norm_w, float eps, char* smem, HOOK issued = HOOK()) {
-    static_assert(NWR * NWK == 8, "row2_core: 512 threads");
+    static_assert(NC == 2 || NC == 4, "rows_core: two or four rows");
+    static_assert(NWR * NWK == 8, "rows_core: 512 threads");
+    static_assert(SPLIT || !NORM, "rows_core: the serial form carries no RMSNorm");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave % NWR, wk = wave / NWR;
@@ -519,9 +527,9 @@ __device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int t
     const bool active = tl < nitems;
     const int k = ks0 * 32 + tl * IW;
     char* stage = smem;
-    char* xch = smem + R2_STAGE_BYTES(nks);
-    float* sqs = reinterpret_cast<float*>(xch + R1_XCH_BYTES);     // [8] per-wave sums of squares (SPLIT: waves 0..3 row 0, 4..7 row 1)
-    float* red = reinterpret_cast<float*>(xch + R1_XCH_BYTES + 32);   // [2 rows][NWK][NWR][4 quarters][4]
+    char* xch = smem + ROWS_STAGE_BYTES(NC, nks);
+    float* sqs = reinterpret_cast<float*>(xch + R1_XCH_BYTES);     // [NC rows][4 waves of the row's half]
+    float* red = reinterpret_cast<float*>(xch + R1_XCH_BYTES + NC * 16);   // [NC rows][NWK][NWR][4 quarters][4]
     f32x8 g0 = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
     if (NORM && active) {
         if (IW == 8) g0 = *reinterpret_cast<const f32x8*>(norm_w + k);
@@ -534,11 +542,12 @@ __device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int t
 #pragma unroll
     for (int i = 0; i < MAXKS; i++) {
         const s16x8* wp_ = reinterpret_cast<const s16x8*>(wbase + (size_t)(i < nw ? i : (nw > 0 ? nw - 1 : 0)) * 1024 + wlane);
-        abuf[i] = ld_wfrag<NT>(wp_);       // several pairs: the sibling chains' blocks of this tile follow on this XCD -> keep it in L2
+        abuf[i] = ld_wfrag<NT>(wp_);       // several chains: the sibling chains' blocks of this tile follow on this XCD -> keep it in L2
     }
     __builtin_amdgcn_sched_barrier(0);
     issued();
-    if (tid < 2) reinterpret_cast<volatile int*>(xch)[tid] = 0;     // the providers' arming words (OpGran::nobar)
+    volatile int* aw = reinterpret_cast<volatile int*>(xch);       // the providers' arming words (OpGran::nobar)
+    if (tid < NC) aw[tid] = 0;
     __syncthreads();
     auto put = [&](f32x8 v, int col) {                            // the row's hi / lo planes into column `col` of the operand stage
         if (!active) return;
@@ -546,14 +555,14 @@ __device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int t
         bf16x8 hi, lo;
         split8(v, hi, lo);
         if (IW == 8) {
-            bf16x8* dst = reinterpret_cast<bf16x8*>(stage + (size_t)(tl >> 2) * 256 + col * 64) + (tl & 3);
+            bf16x8* dst = reinterpret_cast<bf16x8*>(stage + (size_t)(tl >> 2) * (NC * 128) + col * 64) + (tl & 3);
             dst[0] = hi;
-            dst[8] = lo;
+            dst[NC * 4] = lo;
         } else {
             typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-            bf16x4* dst = reinterpret_cast<bf16x4*>(stage + (size_t)(tl >> 3) * 256 + col * 64) + (tl & 7);
+            bf16x4* dst = reinterpret_cast<bf16x4*>(stage + (size_t)(tl >> 3) * (NC * 128) + col * 64) + (tl & 7);
             dst[0] = __builtin_shufflevector(hi, hi, 0, 1, 2, 3);
-            dst[16] = __builtin_shufflevector(lo, lo, 0, 1, 2, 3);
+            dst[NC * 8] = __builtin_shufflevector(lo, lo, 0, 1, 2, 3);
         }
     };
     auto sumsq = [&](const f32x8& v) {
@@ -564,32 +573,51 @@ __device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int t
         }
         return wave_sum(sq);
     };
-    if constexpr (SPLIT) {
-        f32x8 v = half == 0 ? op0.finish(k, hw, nitems, active, xch) : op1.finish(k, hw, nitems, active, xch);
-        if (NORM) { const float sq = sumsq(v); if (lane == 0) sqs[wave] = sq; }
-        put(v, half);
+    // The gathers are where the two forms differ (kept apart: merging them changes their timing).
+    if constexpr (NC == 2) {
+        if constexpr (SPLIT) {                                    // one row per half, the blocking provider only
+            f32x8 v = half == 0 ? ops[0].finish(k, hw, nitems, active, xch) : ops[1].finish(k, hw, nitems, active, xch);
+            if (NORM) { const float sq = sumsq(v); if (lane == 0) sqs[wave] = sq; }      // (wave = 4 half + hw: row `half`, wave hw of its half)
+            put(v, half);
+        } else {                                                  // both rows by all threads: the one attempt reads the granules directly (IW == 8 only)
+            f32x8 v0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v1 = v0;
+            bool both = false;
+            if (IW == 8 && ops[0].G->spec) {
+                bool ok = true;
+                if (active) { ok = ops[0].G->ld8(ops[0].g0 + k, v0); ok &= ops[1].G->ld8(ops[1].g0 + k, v1); }
+                both = __all(ok) && hw * 64 < nitems;
+            }
+            if (both) { if (hw == 0 && lane == 0) { aw[ops[0].grp] = 1; aw[ops[1].grp] = 1; } }      // (the leader wave arms both words for the waves that go the blocking way)
+            else { v0 = ops[0].finish(k, hw, nitems, active, xch); v1 = ops[1].finish(k, hw, nitems, active, xch); }
+            put(v0, 0);
+            put(v1, 1);
+        }
     } else {
-        static_assert(SPLIT || !NORM, "row2_core: the serial form carries no RMSNorm");
-        // both rows' vectors were published by the same producer blocks at the same time: one attempt with both rows' loads in flight
-        // together (one round trip); a wave whose attempt fails fetches them one after the other the blocking way
-        f32x8 v0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v1 = v0;
-        bool both = false;
-        if (IW == 8 && op0.G->spec) {
-            bool ok = true;
-            if (active) { ok = op0.G->ld8(op0.g0 + k, v0); ok &= op1.G->ld8(op1.g0 + k, v1); }
-            both = __all(ok) && hw * 64 < nitems;
-        }
-        if (both) {                       // (the leader wave arms both words for the waves that go the blocking way)
-            if (hw == 0 && lane == 0) { volatile int* aw = reinterpret_cast<volatile int*>(xch); aw[op0.grp] = 1; aw[op1.grp] = 1; }
-        } else { v0 = op0.finish(k, hw, nitems, active, xch); v1 = op1.finish(k, hw, nitems, active, xch); }
-        put(v0, 0);
-        put(v1, 1);
+        auto pair = [&](OP& oa, OP& ob, int ra, int rb) {         // rows ra, rb of this thread group: fetch, (sum of squares), stage
+            f32x8 va, vb;                                         // (the providers by reference: a run-time index into ops[] puts the array in scratch)
+            bool both = false;
+            if (oa.G->spec) {
+                bool ok = oa.attempt(k, active, va);
+                ok &= ob.attempt(k, active, vb);
+                both = __all(ok) && hw * 64 < nitems;
+            }
+            if (both) { if (hw == 0 && lane == 0) { aw[ra] = 1; aw[rb] = 1; } }      // (the leader wave arms the rows' words for waves that go the blocking way)
+            else { va = oa.finish(k, hw, nitems, active, xch); vb = ob.finish(k, hw, nitems, active, xch); }
+            if (NORM) {
+                const float sa = sumsq(va), sb = sumsq(vb);
+                if (lane == 0) { sqs[ra * 4 + hw] = sa; sqs[rb * 4 + hw] = sb; }
+            }
+            put(va, ra);
+            put(vb, rb);
+        };
+        if constexpr (SPLIT) { if (half == 0) pair(ops[0], ops[1], 0, 1); else pair(ops[2], ops[3], 2, 3); }
+        else { pair(ops[0], ops[1], 0, 1); pair(ops[2], ops[3], 2, 3); }
     }
     __syncthreads();
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const s16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
     constexpr int GRP = MAXKS <= 7 ? MAXKS : (MAXKS + 1) / 2;
-    const int bcol = (lane & 15) == 1 ? 64 : 0;                   // B operand: column n = lane & 15 -> row n (columns >= 2 read row 0, results unused)
+    const int bcol = ((lane & 15) < NC ? lane & 15 : 0) * 64;        // B operand: column n = lane & 15 -> row n (columns >= NC read row 0, results unused)
 #pragma unroll
     for (int gg = 0; gg < MAXKS; gg += GRP) {
         bf16x8 bh[GRP], bl[GRP];
@@ -598,9 +626,9 @@ __device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int t
             const int i = gg + j;
             if (i < MAXKS) {
                 const int s_ = (w0 + i < w1 ? w0 + i : w1 - 1) - ks0;
-                const bf16x8* xb = reinterpret_cast<const bf16x8*>(stage + (size_t)s_ * 256 + bcol) + (lane >> 4);
+                const bf16x8* xb = reinterpret_cast<const bf16x8*>(stage + (size_t)s_ * (NC * 128) + bcol) + (lane >> 4);
                 bh[j] = xb[0];
-                bl[j] = xb[8];
+                bl[j] = xb[NC * 4];
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -615,143 +643,10 @@ __device__ __forceinline__ float row2_core(const uint16_t* __restrict__ W, int t
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if ((lane & 15) < 2) *reinterpret_cast<f32x4*>(red + (lane & 15) * (NWK * NWR * 16) + ((wk * NWR + wr) * 4 + (lane >> 4)) * 4) = acc;
+    if ((lane & 15) < NC) *reinterpret_cast<f32x4*>(red + (lane & 15) * (NWK * NWR * 16) + ((wk * NWR + wr) * 4 + (lane >> 4)) * 4) = acc;
     __syncthreads();
     float out = 0.f;
-    if (tid < 2 * NWR * 16) {
-        const int c = tid / (NWR * 16), t = tid - c * (NWR * 16);
-        const int wr_ = t >> 4, q = (t >> 2) & 3, r_ = t & 3;
-        const float* rc = red + c * (NWK * NWR * 16);
-        out = rc[((0 * NWR + wr_) * 4 + q) * 4 + r_];
-#pragma unroll
-        for (int j = 1; j < NWK; j++) out += rc[((j * NWR + wr_) * 4 + q) * 4 + r_];
-        if (NORM) out *= rsqrtf(((sqs[4 * c] + sqs[4 * c + 1]) + (sqs[4 * c + 2] + sqs[4 * c + 3])) / (float)K + eps);
-    }
-    return out;
-}
-
-// ---- four rows per block (k_step4): columns 0 .. 3 of the MFMA's B operand.  SPLIT (operands of <= 256 items): half h of the block
-// serves rows 2 h and 2 h + 1 -- one attempt with both rows' loads in flight (the rows' producers publish together), the blocking
-// providers one after the other where that fails; otherwise (down projection) all threads take rows (0, 1), then (2, 3) the same way.
-// ops[r].grp must be r (own arming word per row, cleared here), OpGran::nobar set.  Returns feature f of row c in thread c * NWR * 16 + f.
-#define R4_STAGE_BYTES(nks) ((nks) * 512)
-__device__ __host__ constexpr int r4_smem_bytes(int nks) { return R4_STAGE_BYTES(nks) + R1_XCH_BYTES + 64 + 4 * 8 * 4 * 16; }
-template <int NWR, int NWK, int MAXKS, bool NORM, bool SPLIT, bool NT, class OP, class HOOK = R1NoHook>
-__device__ __forceinline__ float row4_core(const uint16_t* __restrict__ W, int tile0, int tstride, int KS, int K, int ks0, int ks1, OP (&ops)[4],
-                                           const float* norm_w, float eps, char* smem, HOOK issued = HOOK()) {
-    static_assert(NWR * NWK == 8, "row4_core: 512 threads");
-    static_assert(SPLIT || !NORM, "row4_core: the serial form carries no RMSNorm");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave % NWR, wk = wave / NWR;
-    const int nks = ks1 - ks0;
-    const int w0 = ks0 + (nks * wk) / NWK, w1 = ks0 + (nks * (wk + 1)) / NWK;
-    constexpr int IW = OP::IW;
-    const int nitems = nks * (32 / IW);
-    const int half = SPLIT ? (wave >> 2) : 0;
-    const int tl = SPLIT ? (tid & 255) : tid, hw = SPLIT ? (wave & 3) : wave;
-    const bool active = tl < nitems;
-    const int k = ks0 * 32 + tl * IW;
-    char* stage = smem;
-    char* xch = smem + R4_STAGE_BYTES(nks);
-    float* sqs = reinterpret_cast<float*>(xch + R1_XCH_BYTES);     // [4 rows][4 waves of the row's half]
-    float* red = reinterpret_cast<float*>(xch + R1_XCH_BYTES + 64);   // [4 rows][NWK][NWR][4 quarters][4]
-    f32x8 g0 = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-    if (NORM && active) {
-        if (IW == 8) g0 = *reinterpret_cast<const f32x8*>(norm_w + k);
-        else { const f32x4 g4 = *reinterpret_cast<const f32x4*>(norm_w + k); g0[0] = g4[0]; g0[1] = g4[1]; g0[2] = g4[2]; g0[3] = g4[3]; }
-    }
-    const char* wbase = reinterpret_cast<const char*>(W) + ((size_t)(tile0 + wr * tstride) * KS + w0) * 1024;
-    const unsigned wlane = lane * 16;
-    s16x8 abuf[MAXKS];
-    const int nw = w1 - w0;
-#pragma unroll
-    for (int i = 0; i < MAXKS; i++) {
-        const s16x8* wp_ = reinterpret_cast<const s16x8*>(wbase + (size_t)(i < nw ? i : (nw > 0 ? nw - 1 : 0)) * 1024 + wlane);
-        abuf[i] = ld_wfrag<NT>(wp_);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    issued();
-    volatile int* aw = reinterpret_cast<volatile int*>(xch);
-    if (tid < 4) aw[tid] = 0;
-    __syncthreads();
-    auto put = [&](f32x8 v, int col) {
-        if (!active) return;
-        if (NORM) v = g0 * v;
-        bf16x8 hi, lo;
-        split8(v, hi, lo);
-        if (IW == 8) {
-            bf16x8* dst = reinterpret_cast<bf16x8*>(stage + (size_t)(tl >> 2) * 512 + col * 64) + (tl & 3);
-            dst[0] = hi;
-            dst[16] = lo;
-        } else {
-            typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-            bf16x4* dst = reinterpret_cast<bf16x4*>(stage + (size_t)(tl >> 3) * 512 + col * 64) + (tl & 7);
-            dst[0] = __builtin_shufflevector(hi, hi, 0, 1, 2, 3);
-            dst[32] = __builtin_shufflevector(lo, lo, 0, 1, 2, 3);
-        }
-    };
-    auto sumsq = [&](const f32x8& v) {
-        float sq = 0.f;
-        if (active) {
-            sq = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-            if (IW == 8) sq += (v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]);
-        }
-        return wave_sum(sq);
-    };
-    auto pair = [&](OP& oa, OP& ob, int ra, int rb) {             // rows ra, rb of this thread group: fetch, (sum of squares), stage
-        f32x8 va, vb;                                             // (the providers by reference: a run-time index into ops[] puts the array in scratch)
-        bool both = false;
-        if (oa.G->spec) {
-            bool ok = oa.attempt(k, active, va);
-            ok &= ob.attempt(k, active, vb);
-            both = __all(ok) && hw * 64 < nitems;
-        }
-        if (both) { if (hw == 0 && lane == 0) { aw[ra] = 1; aw[rb] = 1; } }      // (the leader wave arms the rows' words for waves that go the blocking way)
-        else { va = oa.finish(k, hw, nitems, active, xch); vb = ob.finish(k, hw, nitems, active, xch); }
-        if (NORM) {
-            const float sa = sumsq(va), sb = sumsq(vb);
-            if (lane == 0) { sqs[ra * 4 + hw] = sa; sqs[rb * 4 + hw] = sb; }
-        }
-        put(va, ra);
-        put(vb, rb);
-    };
-    if constexpr (SPLIT) { if (half == 0) pair(ops[0], ops[1], 0, 1); else pair(ops[2], ops[3], 2, 3); }
-    else { pair(ops[0], ops[1], 0, 1); pair(ops[2], ops[3], 2, 3); }
-    __syncthreads();
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const s16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    constexpr int GRP = MAXKS <= 7 ? MAXKS : (MAXKS + 1) / 2;
-    const int bcol = ((lane & 15) < 4 ? (lane & 15) : 0) * 64;       // B operand: column n = lane & 15 -> row n (columns >= 4 read row 0, results unused)
-#pragma unroll
-    for (int gg = 0; gg < MAXKS; gg += GRP) {
-        bf16x8 bh[GRP], bl[GRP];
-#pragma unroll
-        for (int j = 0; j < GRP; j++) {
-            const int i = gg + j;
-            if (i < MAXKS) {
-                const int s_ = (w0 + i < w1 ? w0 + i : w1 - 1) - ks0;
-                const bf16x8* xb = reinterpret_cast<const bf16x8*>(stage + (size_t)s_ * 512 + bcol) + (lane >> 4);
-                bh[j] = xb[0];
-                bl[j] = xb[16];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < GRP; j++) {
-            const int i = gg + j;
-            if (i < MAXKS) {
-                const bf16x8 a_ = __builtin_bit_cast(bf16x8, w0 + i < w1 ? abuf[i] : zero8);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, bh[j], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, bl[j], acc, 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if ((lane & 15) < 4) *reinterpret_cast<f32x4*>(red + (lane & 15) * (NWK * NWR * 16) + ((wk * NWR + wr) * 4 + (lane >> 4)) * 4) = acc;
-    __syncthreads();
-    float out = 0.f;
-    if (tid < 4 * NWR * 16) {
+    if (tid < NC * NWR * 16) {
         const int c = tid / (NWR * 16), t = tid - c * (NWR * 16);
         const int wr_ = t >> 4, q = (t >> 2) & 3, r_ = t & 3;
         const float* rc = red + c * (NWK * NWR * 16);

@@ -652,13 +652,13 @@ __global__ __launch_bounds__(512) void k_gateup(GateUpArgs a) {
 // Rows of one decode-step launch.  Three forms (all keep every sum of a row in k_step's order, so ids do not depend on the form):
 //   k_step<true>  every row is a chain of k_step's blocks of its own, the rows' chains interleaved in the grid so that the blocks that
 //                 stream one weight tile (one per row) share an XCD and its L2;
-//   k_step2       the rows in pairs: one chain per pair, every GEMV block serves both rows as MFMA columns 0 / 1 (row2_core);
-//   k_step4       the rows in fours: MFMA columns 0 .. 3 (row4_core; the O role stays two rows per block).
+//   k_step_rows<2>  the rows in pairs: one chain per pair, every GEMV block serves both rows as MFMA columns 0 / 1 (rows_core<2>);
+//   k_step_rows<4>  the rows in fours: MFMA columns 0 .. 3 (rows_core<4>; the O role stays two rows per block).
 // Measured on MI355X at the configs[1] context (positions 323 .. 387), us per step (profiles/r4_rows_sweep.txt):
 //   rows            1     2     3     4     6     8    10    12    16    20    24
 //   k_step<true>   332   445   496   590   746   903
-//   k_step2         -    430   564   554   616   708   822   877  1076
-//   k_step4         -     -     -    561   691   709   801   826   921  1065  1175
+//   k_step_rows<2>  -    430   564   554   616   708   822   877  1076
+//   k_step_rows<4>  -     -     -    561   691   709   801   826   921  1065  1175
 //   launches       599   643   734   767   823   888  1000  1064  1162  1181  1205
 // Every chain adds its ~12 600 blocks to a grid of which 512 are resident (2 blocks of 512 threads per CU at 109-125 VGPRs): ~80 us
 // per one-row chain, ~92 us per pair, ~120-150 us per four (their operand gathers are 2 / 4 x a row's: the Q role's x + 2 partials is
@@ -1216,19 +1216,22 @@ __global__ __launch_bounds__(R1_THREADS) void k_step1(StepArgs a) {
     }
 }
 
-// ------------------------------------------------------------------ k_step2: 2 .. CH_MAX_ROWS rows in one launch, two rows per block
-// The rows are taken in PAIRS: a pair is one chain of k_step's blocks in which every GEMV block serves both rows at once -- the rows are
-// columns 0 and 1 of the MFMA's B operand (row2_core, chain.h), the block's weight fragments are fetched once, the two rows' operands are
-// gathered by the two halves of the block side by side; hand-off buffers, slot (state record, KV cache, pending input) and epilogue are
-// per row.  The attention role has no weights to share: its tiles stay one block per (row, tile, kv head).  ceil(R / 2) pairs are
-// interleaved in the grid like the rows of k_step<true> (an odd row count: the last pair's second column repeats its first row and is
-// not published).  Per row every sum runs in k_step's order, so the ids do not depend on which kernel served a row.
-template <bool NT>
-__global__ __launch_bounds__(R1_THREADS) void k_step2(StepArgs a) {
+// ------------------------------------------------------------------ k_step_rows: 2 .. CH_MAX_ROWS rows in one launch, NC (2 or 4) rows per block
+// The rows are taken in groups of NC: a group is one chain of k_step's blocks in which every GEMV block serves all its rows at once -- the
+// rows are columns 0 .. NC - 1 of the MFMA's B operand (rows_core, chain.h), the block's weight fragments are fetched once, the rows'
+// operands are gathered by the two halves of the block side by side (the down projection: by all threads, two rows at a time); hand-off
+// buffers, slot (state record, KV cache, pending input) and epilogue are per row.  The attention role has no weights to share: its tiles
+// stay one block per (row, tile, kv head).  The O role is two rows per block at either NC (its provider merges attention tiles in several
+// dependent sweeps): at four rows two blocks per chain, rows (0, 1) and (2, 3), the second finds W_o in L2.  ceil(R / NC) chains are
+// interleaved in the grid like the rows of k_step<true>; a last chain whose rows do not all exist repeats its first row in the empty
+// columns and does not publish them.  Per row every sum runs in k_step's order, so the ids do not depend on which kernel served a row.
+template <int NC, bool NT>
+__global__ __launch_bounds__(R1_THREADS) void k_step_rows(StepArgs a) {
+    static_assert((NC == 2 || NC == 4) && NC <= GRAN_ROWS, "k_step_rows: two or four rows per chain");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, gb = blockIdx.x, R = a.n_rows, P = (R + 1) >> 1, H = a.H;
-    const int nQ = 2 * (a.n_q + 2 * a.n_kv), nA1 = a.ntiles * a.n_kv, nA = 2 * nA1, nO = H / 16, nGU = a.inter / 16;
-    const int per = a.per + nA1;
+    const int tid = threadIdx.x, gb = blockIdx.x, R = a.n_rows, P = (R + NC - 1) >> (NC / 2), H = a.H;      // (NC / 2 = log2 NC at 2 and 4)
+    const int nQ = 2 * (a.n_q + 2 * a.n_kv), nA1 = a.ntiles * a.n_kv, nA = NC * nA1, nO1 = H / 16, nO = (NC / 2) * nO1, nGU = a.inter / 16;
+    const int per = a.per + (NC - 1) * nA1 + (NC / 2 - 1) * nO1;
     const int lb = per * P;
     const int layer = min(gb / lb, a.n_layers);
     int r, chain;
@@ -1238,148 +1241,37 @@ __global__ __launch_bounds__(R1_THREADS) void k_step2(StepArgs a) {
         if (g8 < full) { const int rem = q - g8 * 8 * P; chain = rem >> 3; r = g8 * 8 + (rem & 7); }
         else { const int rem = q - full * 8 * P, m = nb - full * 8; chain = rem / m; r = full * 8 + rem - chain * m; }
     }
-    const bool two = 2 * chain + 1 < R;
-    const int row0 = 2 * chain, row1 = two ? row0 + 1 : row0;
-    const int slot0 = a.row_slots ? a.row_slots[row0] : row0, slot1 = a.row_slots ? a.row_slots[row1] : row1;
-    const unsigned go0 = (unsigned)row0 * a.row_gran, go1 = (unsigned)row1 * a.row_gran;
-    Gran G;
-    G.init(a.gran, a.gran_bytes * (unsigned)R, *a.epoch, a.err + slot0 * ST, a.spec != 0);
-    G.set_err2(a.err + slot1 * ST);
-    const unsigned gl = (unsigned)min(layer, a.n_layers - 1) * a.gl;
-    const unsigned gp = layer > 0 ? (unsigned)(layer - 1) * a.gl : 0u;
-    const int c32 = (tid >> 5) & 1, c16 = (tid >> 4) & 1;          // the row of an epilogue thread: 32 (NWR = 2) / 16 (NWR = 1) features per row
-    if (layer >= a.n_layers) {      // head
-        OpFold op0{&G, go0 + gl, go0 + gl + a.off_dg, H, nullptr, -1, go0 + gl + a.off_dg + H - 1};
-        OpFold op1{&G, go1 + gl, go1 + gl + a.off_dg, H, nullptr, -1, go1 + gl + a.off_dg + H - 1};
-        const float out = row2_core<1, 8, 4, true, true, NT>(a.wdec, r, 0, H / 32, H, 0, H / 32, op0, op1, a.final_norm, a.eps, smem);
-        if (tid < 32 && (c16 == 0 || two)) a.logits[(size_t)(c16 ? row1 : row0) * a.ldl + r * 16 + (tid & 15)] = out + a.bdec[r * 16 + (tid & 15)];
-        return;
-    }
-    const StepLayer L = step_layer(a.layers, layer);
-    OpFold xin0{&G, go0 + gp, go0 + gp + a.off_dg, H, layer == 0 ? a.xin + (size_t)row0 * H : nullptr, -1, go0 + gp + a.off_hg + a.inter - 1};
-    OpFold xin1{&G, go1 + gp, go1 + gp + a.off_dg, H, layer == 0 ? a.xin + (size_t)row1 * H : nullptr, -1, go1 + gp + a.off_hg + a.inter - 1};
-    if (r < nQ) {                   // ---- Q
-        const int head = r >> 1, half = r & 1;
-        const int slot = c32 ? slot1 : slot0;
-        const int pos = a.state[slot * ST + CV2_ST_POS];
-        const int f = half * 16 + ((tid >> 4) & 1) * 32 + (tid & 15);
-        const float bias = L.bqkv[head * 64 + f];
-        float c, sn;
-        auto hook = [&]() { c = a.cosT[pos * 32 + (f & 31)]; sn = a.sinT[pos * 32 + (f & 31)]; };
-        float v = row2_core<2, 4, 7, true, true, NT>(L.wqkv, head * 4 + half, 2, H / 32, H, 0, H / 32, xin0, xin1, L.ln1, a.eps, smem, hook) + bias;
-        const float vp = __shfl(v, (tid & 63) ^ 16);
-        if (head < a.n_q + a.n_kv) v = (f < 32) ? (v * c - vp * sn) : (v * c + vp * sn);
-        if (*a.dbg_skip == ((layer << 16) | r) + 1) return;    // (test hook, as in k_step: Q block r of this layer keeps its results to itself)
-        if (tid < 64 && (c32 == 0 || two)) {
-            const unsigned o = (c32 ? go1 : go0) + gl;
-            if (head < a.n_q) G.store(o + a.off_qg + head * 64 + f, v);
-            else if (head < a.n_q + a.n_kv) {
-                const int kvh = head - a.n_q;
-                G.store(o + a.off_kv + kvh * 64 + f, v);
-                L.kc[(size_t)slot * a.kv_slot + ((size_t)kvh * a.max_pos + pos) * 64 + f] = v;
-            } else {
-                const int kvh = head - a.n_q - a.n_kv;
-                G.store(o + a.off_kv + (a.n_kv + kvh) * 64 + f, v);
-                L.vc[(size_t)slot * a.kv_slot + ((size_t)kvh * a.max_pos + pos) * 64 + f] = v;
-            }
-        }
-        return;
-    }
-    r -= nQ;
-    if (r < nA) {                   // ---- A: one tile of one kv head of one row
-        const int c = r / nA1, rr = r - c * nA1;
-        if (c == 1 && !two) return;
-        const int tile = rr / a.n_kv, g = rr - tile * a.n_kv;
-        const int slot = c ? slot1 : slot0;
-        const int pos = a.state[slot * ST + CV2_ST_POS];
-        if (tile * AT_TILE >= pos) return;
-        if (c) G.err = G.err2;
-        const unsigned o = c ? go1 : go0;
-        if (layer > 0 && !G.spec) G.wait(o + gp + a.off_dg + H - 1, H, CH_NP);
-        attn_role(G, L.kc + (size_t)slot * a.kv_slot + (size_t)g * a.max_pos * 64, L.vc + (size_t)slot * a.kv_slot + (size_t)g * a.max_pos * 64, pos,
-                  tile * AT_TILE, a.rep, o + gl + a.off_qg + g * a.rep * 64, o + gl + a.off_ag + (unsigned)rr * AT_GSTRIDE, smem, -1);
-        return;
-    }
-    r -= nA;
-    if (r < nO) {                   // ---- O
-        const int pos0 = a.state[slot0 * ST + CV2_ST_POS], pos1 = a.state[slot1 * ST + CV2_ST_POS];
-        OpAtt op0{&G, go0 + gl + a.off_ag, a.n_kv, a.rep, (pos0 + AT_TILE - 1) / AT_TILE, -1, &xin0, r * 16, go0 + gl + a.off_qg, go0 + gl + a.off_kv, 0, 0};
-        OpAtt op1{&G, go1 + gl + a.off_ag, a.n_kv, a.rep, (pos1 + AT_TILE - 1) / AT_TILE, -1, &xin1, r * 16, go1 + gl + a.off_qg, go1 + gl + a.off_kv, 256, 1};
-        const float ov = row2_core<1, 8, 4, false, true, NT>(L.wo, r, 0, a.NQ / 32, a.NQ, 0, a.NQ / 32, op0, op1, nullptr, 0.f, smem);
-        if (tid < 32 && (c16 == 0 || two))
-            G.store((c16 ? go1 : go0) + gl + r * 16 + (tid & 15), reinterpret_cast<const float*>(smem + R2_STAGE_BYTES(a.NQ / 32))[1200 + c16 * 16 + (tid & 15)] + ov);
-        return;
-    }
-    r -= nO;
-    if (r < nGU) {                  // ---- GU
-        OpGran<4> op0{&G, go0 + gl, go0 + gl + 15, 0, -1, 0, true};
-        OpGran<4> op1{&G, go1 + gl, go1 + gl + 15, 0, -1, 1, true};
-        const float v = row2_core<2, 4, 7, true, true, NT>(L.wgu, r * 2, 1, H / 32, H, 0, H / 32, op0, op1, L.ln2, a.eps, smem);
-        const float u = __shfl(v, (tid & 15) + 16 + 32 * c32);     // threads 0..15 hold gate, 16..31 up of row 0; 32..47 / 48..63 of row 1 (wave 0)
-        if (tid < 64 && (tid & 31) < 16 && (c32 == 0 || two)) G.store((c32 ? go1 : go0) + gl + a.off_hg + r * 16 + (tid & 15), (v / (1.f + __expf(-v))) * u);
-        return;
-    }
-    r -= nGU;
-    {                               // ---- D
-        const int sp = r / nO, tile = r - sp * nO;
-        const int KS = a.inter / 32;
-        const int ks0 = (int)(((unsigned)KS * sp) / CH_NP), ks1 = (int)(((unsigned)KS * (sp + 1)) / CH_NP);
-        OpGran<8> op0{&G, go0 + gl + a.off_hg, go0 + gl + a.off_hg + ks0 * 32 + 15, 0, -1, 0, true};
-        OpGran<8> op1{&G, go1 + gl + a.off_hg, go1 + gl + a.off_hg + ks0 * 32 + 15, 0, -1, 1, true};     // (own arming word: no barrier separates the two fetches)
-        const float v = row2_core<1, 8, 10, false, false, NT>(L.wdown, tile, 0, KS, a.inter, ks0, ks1, op0, op1, nullptr, 0.f, smem);
-        if (tid < 32 && (c16 == 0 || two)) G.store((c16 ? go1 : go0) + gl + a.off_dg + sp * H + tile * 16 + (tid & 15), v);
-    }
-}
-
-// ------------------------------------------------------------------ k_step4: rows in groups of FOUR, four MFMA columns per GEMV block
-// As k_step2 with row4_core: one chain of blocks per four rows.  The Q / gate-up / head blocks serve the four rows with the block's
-// halves taking two rows each (both rows' operand loads in flight together), the down projection takes (0, 1) then (2, 3); the O role
-// keeps k_step2's two-row blocks (its provider merges attention tiles in several dependent sweeps: two blocks per chain, rows (0, 1)
-// and (2, 3), the second finds W_o in L2); attention tiles: one block per (row, tile, kv head).  A chain whose last rows do not exist
-// (row count not a multiple of 4) repeats its first row in the empty columns and does not publish them.
-template <bool NT>
-__global__ __launch_bounds__(R1_THREADS) void k_step4(StepArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, gb = blockIdx.x, R = a.n_rows, P = (R + 3) >> 2, H = a.H;
-    const int nQ = 2 * (a.n_q + 2 * a.n_kv), nA1 = a.ntiles * a.n_kv, nA = 4 * nA1, nO1 = H / 16, nO = 2 * nO1, nGU = a.inter / 16;
-    const int per = a.per + 3 * nA1 + nO1;
-    const int lb = per * P;
-    const int layer = min(gb / lb, a.n_layers);
-    int r, chain;
-    {
-        const int q = gb - layer * lb;
-        const int nb = layer < a.n_layers ? per : a.head_blocks, full = nb >> 3, g8 = q / (8 * P);
-        if (g8 < full) { const int rem = q - g8 * 8 * P; chain = rem >> 3; r = g8 * 8 + (rem & 7); }
-        else { const int rem = q - full * 8 * P, m = nb - full * 8; chain = rem / m; r = full * 8 + rem - chain * m; }
-    }
-    const int nv = min(4, R - 4 * chain);                        // rows of this chain that exist
-    int row[4], slot[4]; unsigned go[4];
+    const int nv = min(NC, R - NC * chain);                      // rows of this chain that exist
+    int row[NC], slot[NC]; unsigned go[NC];
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-        row[c] = 4 * chain + (c < nv ? c : 0);
+    for (int c = 0; c < NC; c++) {
+        row[c] = c < nv ? NC * chain + c : NC * chain;
         slot[c] = a.row_slots ? a.row_slots[row[c]] : row[c];
         go[c] = (unsigned)row[c] * a.row_gran;
     }
     Gran G;
     G.init(a.gran, a.gran_bytes * (unsigned)R, *a.epoch, a.err + slot[0] * ST, a.spec != 0);
 #pragma unroll
-    for (int c = 0; c < 4; c++) G.errs[c] = a.err + slot[c] * ST;      // a block that gives up flags every row of its chain (rows >= nv repeat slot[0])
+    for (int c = 0; c < GRAN_ROWS; c++) G.errs[c] = a.err + slot[c % NC] * ST;      // a block that gives up flags every row of its chain (rows >= nv repeat slot[0])
     const unsigned gl = (unsigned)min(layer, a.n_layers - 1) * a.gl;
     const unsigned gp = layer > 0 ? (unsigned)(layer - 1) * a.gl : 0u;
-    const int c32 = (tid >> 5) & 3, c16 = (tid >> 4) & 3;          // the row of an epilogue thread (NWR = 2: 32 features per row, NWR = 1: 16)
-    auto sel = [&](int c, auto& arr) { return c == 0 ? arr[0] : c == 1 ? arr[1] : c == 2 ? arr[2] : arr[3]; };
+    const int c32 = (tid >> 5) & (NC - 1), c16 = (tid >> 4) & (NC - 1);      // the row of an epilogue thread (NWR = 2: 32 features per row, NWR = 1: 16)
+    auto sel = [&](int c, auto& arr) {                           // arr[c] without a run-time index (which would put the array in scratch; so does a loop of compares)
+        if constexpr (NC == 2) { const auto a0 = arr[0], a1 = arr[1]; return c == 0 ? a0 : a1; }
+        else return c == 0 ? arr[0] : c == 1 ? arr[1] : c == 2 ? arr[2] : arr[3];
+    };
     if (layer >= a.n_layers) {      // head
-        OpFold ops[4];
+        OpFold ops[NC];
 #pragma unroll
-        for (int c = 0; c < 4; c++) ops[c] = OpFold{&G, go[c] + gl, go[c] + gl + a.off_dg, H, nullptr, -1, go[c] + gl + a.off_dg + H - 1};
-        const float out = row4_core<1, 8, 4, true, true, NT>(a.wdec, r, 0, H / 32, H, 0, H / 32, ops, a.final_norm, a.eps, smem);
-        if (tid < 64 && c16 < nv) a.logits[(size_t)sel(c16, row) * a.ldl + r * 16 + (tid & 15)] = out + a.bdec[r * 16 + (tid & 15)];
+        for (int c = 0; c < NC; c++) ops[c] = OpFold{&G, go[c] + gl, go[c] + gl + a.off_dg, H, nullptr, -1, go[c] + gl + a.off_dg + H - 1};
+        const float out = rows_core<NC, 1, 8, 4, true, true, NT>(a.wdec, r, 0, H / 32, H, 0, H / 32, ops, a.final_norm, a.eps, smem);
+        if (tid < NC * 16 && c16 < nv) a.logits[(size_t)sel(c16, row) * a.ldl + r * 16 + (tid & 15)] = out + a.bdec[r * 16 + (tid & 15)];
         return;
     }
     const StepLayer L = step_layer(a.layers, layer);
-    OpFold xin[4];
+    OpFold xin[NC];
 #pragma unroll
-    for (int c = 0; c < 4; c++)
+    for (int c = 0; c < NC; c++)
         xin[c] = OpFold{&G, go[c] + gp, go[c] + gp + a.off_dg, H, layer == 0 ? a.xin + (size_t)row[c] * H : nullptr, -1, go[c] + gp + a.off_hg + a.inter - 1};
     if (r < nQ) {                   // ---- Q
         const int head = r >> 1, half = r & 1;
@@ -1389,11 +1281,11 @@ __global__ __launch_bounds__(R1_THREADS) void k_step4(StepArgs a) {
         const float bias = L.bqkv[head * 64 + f];
         float c, sn;
         auto hook = [&]() { c = a.cosT[pos * 32 + (f & 31)]; sn = a.sinT[pos * 32 + (f & 31)]; };
-        float v = row4_core<2, 4, 7, true, true, NT>(L.wqkv, head * 4 + half, 2, H / 32, H, 0, H / 32, xin, L.ln1, a.eps, smem, hook) + bias;
+        float v = rows_core<NC, 2, 4, 7, true, true, NT>(L.wqkv, head * 4 + half, 2, H / 32, H, 0, H / 32, xin, L.ln1, a.eps, smem, hook) + bias;
         const float vp = __shfl(v, (tid & 63) ^ 16);
         if (head < a.n_q + a.n_kv) v = (f < 32) ? (v * c - vp * sn) : (v * c + vp * sn);
-        if (*a.dbg_skip == ((layer << 16) | r) + 1) return;    // (test hook, as in k_step)
-        if (tid < 128 && c32 < nv) {
+        if (*a.dbg_skip == ((layer << 16) | r) + 1) return;    // (test hook, as in k_step: Q block r of this layer keeps its results to itself)
+        if (tid < NC * 32 && c32 < nv) {
             const unsigned o = sel(c32, go) + gl;
             if (head < a.n_q) G.store(o + a.off_qg + head * 64 + f, v);
             else if (head < a.n_q + a.n_kv) {
@@ -1416,7 +1308,7 @@ __global__ __launch_bounds__(R1_THREADS) void k_step4(StepArgs a) {
         const int sl = sel(c, slot);
         const int pos = a.state[sl * ST + CV2_ST_POS];
         if (tile * AT_TILE >= pos) return;
-        G.err = G.err2 = a.err + sl * ST;
+        G.err = a.err + sl * ST;
         const unsigned o = sel(c, go);
         if (layer > 0 && !G.spec) G.wait(o + gp + a.off_dg + H - 1, H, CH_NP);
         attn_role(G, L.kc + (size_t)sl * a.kv_slot + (size_t)g * a.max_pos * 64, L.vc + (size_t)sl * a.kv_slot + (size_t)g * a.max_pos * 64, pos,
@@ -1424,34 +1316,33 @@ __global__ __launch_bounds__(R1_THREADS) void k_step4(StepArgs a) {
         return;
     }
     r -= nA;
-    if (r < nO) {                   // ---- O: rows (0, 1) or (2, 3) of the chain, two per block as in k_step2
-        const int pr = r / nO1, t = r - pr * nO1;
+    if (r < nO) {                   // ---- O: rows (0, 1) or, in the chain's second set of blocks at four rows, (2, 3)
+        const int pr = NC == 2 ? 0 : r / nO1, t = r - pr * nO1;
         const int ca = 2 * pr, cb = 2 * pr + 1;
         if (ca >= nv) return;
         const bool two = cb < nv;
         const int sa = sel(ca, slot), sb = sel(cb, slot);
         const unsigned ga = sel(ca, go), gb_ = sel(cb, go);
-        G.err = a.err + sa * ST; G.err2 = a.err + sb * ST;
+        G.err = a.err + sa * ST;
         const int pos0 = a.state[sa * ST + CV2_ST_POS], pos1 = a.state[sb * ST + CV2_ST_POS];
-        OpFold& xa = ca == 0 ? xin[0] : xin[2];
-        OpFold& xb = cb == 1 ? xin[1] : xin[3];
-        OpAtt op0{&G, ga + gl + a.off_ag, a.n_kv, a.rep, (pos0 + AT_TILE - 1) / AT_TILE, -1, &xa, t * 16, ga + gl + a.off_qg, ga + gl + a.off_kv, 0, 0};
-        OpAtt op1{&G, gb_ + gl + a.off_ag, a.n_kv, a.rep, (pos1 + AT_TILE - 1) / AT_TILE, -1, &xb, t * 16, gb_ + gl + a.off_qg, gb_ + gl + a.off_kv, 256, 1};
-        const float ov = row2_core<1, 8, 4, false, true, NT>(L.wo, t, 0, a.NQ / 32, a.NQ, 0, a.NQ / 32, op0, op1, nullptr, 0.f, smem);
+        OpFold& xa = pr == 0 ? xin[0] : xin[NC - 2];
+        OpFold& xb = pr == 0 ? xin[1] : xin[NC - 1];
+        OpAtt ops[2] = {{&G, ga + gl + a.off_ag, a.n_kv, a.rep, (pos0 + AT_TILE - 1) / AT_TILE, -1, &xa, t * 16, ga + gl + a.off_qg, ga + gl + a.off_kv, 0, 0},
+                        {&G, gb_ + gl + a.off_ag, a.n_kv, a.rep, (pos1 + AT_TILE - 1) / AT_TILE, -1, &xb, t * 16, gb_ + gl + a.off_qg, gb_ + gl + a.off_kv, 256, 1}};
+        const float ov = rows_core<2, 1, 8, 4, false, true, NT>(L.wo, t, 0, a.NQ / 32, a.NQ, 0, a.NQ / 32, ops, nullptr, 0.f, smem);
         const int e = (tid >> 4) & 1;
         if (tid < 32 && (e == 0 || two))
-            G.store((e ? gb_ : ga) + gl + t * 16 + (tid & 15), reinterpret_cast<const float*>(smem + R2_STAGE_BYTES(a.NQ / 32))[1200 + e * 16 + (tid & 15)] + ov);
+            G.store((e ? gb_ : ga) + gl + t * 16 + (tid & 15), reinterpret_cast<const float*>(smem + ROWS_STAGE_BYTES(2, a.NQ / 32))[1200 + e * 16 + (tid & 15)] + ov);
         return;
     }
     r -= nO;
-    G.err2 = a.err + sel(nv - 1, slot) * ST;
     if (r < nGU) {                  // ---- GU
-        OpGran<4> ops[4];
+        OpGran<4> ops[NC];
 #pragma unroll
-        for (int c = 0; c < 4; c++) ops[c] = OpGran<4>{&G, go[c] + gl, go[c] + gl + 15, 0, -1, c, true};
-        const float v = row4_core<2, 4, 7, true, true, NT>(L.wgu, r * 2, 1, H / 32, H, 0, H / 32, ops, L.ln2, a.eps, smem);
+        for (int c = 0; c < NC; c++) ops[c] = OpGran<4>{&G, go[c] + gl, go[c] + gl + 15, 0, -1, c, true};
+        const float v = rows_core<NC, 2, 4, 7, true, true, NT>(L.wgu, r * 2, 1, H / 32, H, 0, H / 32, ops, L.ln2, a.eps, smem);
         const float u = __shfl(v, (tid & 15) + 16 + 32 * ((tid >> 5) & 1));     // within a wave: rows 2 w, 2 w + 1; gate in lanes 0..15 / 32..47, up in 16..31 / 48..63
-        if (tid < 128 && (tid & 31) < 16 && c32 < nv) G.store(sel(c32, go) + gl + a.off_hg + r * 16 + (tid & 15), (v / (1.f + __expf(-v))) * u);
+        if (tid < NC * 32 && (tid & 31) < 16 && c32 < nv) G.store(sel(c32, go) + gl + a.off_hg + r * 16 + (tid & 15), (v / (1.f + __expf(-v))) * u);
         return;
     }
     r -= nGU;
@@ -1459,11 +1350,11 @@ __global__ __launch_bounds__(R1_THREADS) void k_step4(StepArgs a) {
         const int sp = r / nO1, tile = r - sp * nO1;
         const int KS = a.inter / 32;
         const int ks0 = (int)(((unsigned)KS * sp) / CH_NP), ks1 = (int)(((unsigned)KS * (sp + 1)) / CH_NP);
-        OpGran<8> ops[4];
+        OpGran<8> ops[NC];                                       // (own arming word per row: no barrier separates the fetches)
 #pragma unroll
-        for (int c = 0; c < 4; c++) ops[c] = OpGran<8>{&G, go[c] + gl + a.off_hg, go[c] + gl + a.off_hg + ks0 * 32 + 15, 0, -1, c, true};
-        const float v = row4_core<1, 8, 10, false, false, NT>(L.wdown, tile, 0, KS, a.inter, ks0, ks1, ops, nullptr, 0.f, smem);
-        if (tid < 64 && c16 < nv) G.store(sel(c16, go) + gl + a.off_dg + sp * H + tile * 16 + (tid & 15), v);
+        for (int c = 0; c < NC; c++) ops[c] = OpGran<8>{&G, go[c] + gl + a.off_hg, go[c] + gl + a.off_hg + ks0 * 32 + 15, 0, -1, c, true};
+        const float v = rows_core<NC, 1, 8, 10, false, false, NT>(L.wdown, tile, 0, KS, a.inter, ks0, ks1, ops, nullptr, 0.f, smem);
+        if (tid < NC * 16 && c16 < nv) G.store(sel(c16, go) + gl + a.off_dg + sp * H + tile * 16 + (tid & 15), v);
     }
 }
 
@@ -2821,19 +2712,14 @@ static int get_graph(cv2_llm* h, int n_seqs, int unroll, bool one_launch, hipGra
                     static const bool inter_env = getenv("CV2_CHAIN_MULTI") && getenv("CV2_CHAIN_MULTI")[0] == 'i';     // "inter": one chain per row (k_step<true>)
                     a.spec = n_seqs >= 2 ? spec_env : 0;
                     static const int quad_from = getenv("CV2_CHAIN_QUADS") ? atoi(getenv("CV2_CHAIN_QUADS")) : 9;      // rows from which the chains take four rows (A/B switch)
-                    if (n_seqs >= quad_from && !inter_env) {
-                        const int P = (n_seqs + 3) / 4;
-                        const size_t sm4 = std::max((size_t)r4_smem_bytes(nks_max), (size_t)AT_SMEM_FLOATS * sizeof(float));
-                        const dim3 grid4((d.layers * (a.per + 3 * a.ntiles * d.n_kv + d.hidden / 16) + d.vocab_pad / 16) * P);
-                        if (P == 1 || nt_env) hipLaunchKernelGGL(k_step4<true>, grid4, dim3(R1_THREADS), sm4, cs, a);
-                        else hipLaunchKernelGGL(k_step4<false>, grid4, dim3(R1_THREADS), sm4, cs, a);
-                    } else
-                    if (n_seqs >= 2 && n_seqs != 3 && !inter_env) {  // pairs of rows: two MFMA columns per block (3 rows: one chain per row is faster)
-                        const int P = (n_seqs + 1) / 2;
-                        const size_t sm2 = std::max((size_t)r2_smem_bytes(nks_max), (size_t)AT_SMEM_FLOATS * sizeof(float));
-                        const dim3 grid2((d.layers * (a.per + a.ntiles * d.n_kv) + d.vocab_pad / 16) * P);
-                        if (P == 1 || nt_env) hipLaunchKernelGGL(k_step2<true>, grid2, dim3(R1_THREADS), sm2, cs, a);      // one pair: every weight byte is read once
-                        else hipLaunchKernelGGL(k_step2<false>, grid2, dim3(R1_THREADS), sm2, cs, a);
+                    const bool quads = n_seqs >= quad_from;
+                    if ((quads || (n_seqs >= 2 && n_seqs != 3)) && !inter_env) {       // rows as MFMA columns, in fours or pairs (3 rows: one chain per row is faster)
+                        const int NC = quads ? 4 : 2, P = (n_seqs + NC - 1) / NC;
+                        const size_t smr = std::max((size_t)(NC == 4 ? rows_smem_bytes<4>(nks_max) : rows_smem_bytes<2>(nks_max)), (size_t)AT_SMEM_FLOATS * sizeof(float));
+                        const dim3 gridr((d.layers * (a.per + (NC - 1) * a.ntiles * d.n_kv + (NC / 2 - 1) * (d.hidden / 16)) + d.vocab_pad / 16) * P);
+                        const bool nt = P == 1 || nt_env;                 // one chain: every weight byte is read once
+                        auto kern = NC == 4 ? (nt ? k_step_rows<4, true> : k_step_rows<4, false>) : (nt ? k_step_rows<2, true> : k_step_rows<2, false>);
+                        hipLaunchKernelGGL(kern, gridr, dim3(R1_THREADS), smr, cs, a);
                     } else
                     if (nt_env || n_seqs == 1) hipLaunchKernelGGL((k_step<true, true>), dim3(h->step_blocks * n_seqs), dim3(R1_THREADS), sm, cs, a);
                     else hipLaunchKernelGGL((k_step<true, false>), dim3(h->step_blocks * n_seqs), dim3(R1_THREADS), sm, cs, a);

@@ -198,7 +198,7 @@ def test_hand_off_timeout_commits_nothing_and_the_steps_are_repeated_on_the_laun
 
 
 def test_hand_off_timeout_in_a_two_row_step_fails_no_request(dev, small):
-    """The same broken hand-off inside k_step2 (two requests = one pair of rows per block): the waits behind it time out, BOTH rows'
+    """The same broken hand-off inside k_step_rows<2> (two requests = one pair of rows per block): the waits behind it time out, BOTH rows'
     slots report CV2_ST_ERR = 3 and commit nothing; generate() clears the flags, repeats the steps on the launches and both requests
     finish with the ids of an undisturbed run."""
     from cv2amd import lib as L
@@ -223,7 +223,7 @@ def test_hand_off_timeout_in_a_two_row_step_fails_no_request(dev, small):
 
 @pytest.mark.parametrize('n,q_block', [(3, 2), (9, 5), (11, 0)])
 def test_hand_off_timeout_flags_every_row_of_the_launch(dev, small, n, q_block):
-    """The broken hand-off in the other one-launch forms: 3 rows (k_step<true>, one chain per row) and 9 / 11 rows (k_step4: four rows per
+    """The broken hand-off in the other one-launch forms: 3 rows (k_step<true>, one chain per row) and 9 / 11 rows (k_step_rows<4>: four rows per
     block, the last chain of 11 holds three).  A block that gives up flags EVERY row its chain serves (csrc/chain.h Gran::errs) -- its
     consumers see valid tags on whatever it published and would never time out themselves -- so every row reports CV2_ST_ERR = 3 and
     commits nothing (step, output count and position as after the prefill); generate() repeats the steps on the launches and all requests
@@ -276,11 +276,11 @@ def test_one_row_step_forms_give_the_same_ids(dev, small, monkeypatch, mode):
     assert eng2.generate([req], force_len=40, mode=MODE_RAS, seed=5)[0] == ras
 
 
-@pytest.mark.parametrize('n', [2, 3, 4, 7, 8, 9, 11, 16, 22])
+@pytest.mark.parametrize('n', [2, 3, 4, 6, 7, 8, 9, 10, 11, 16, 22])
 def test_one_launch_rows_equal_the_launches_and_the_oracle(small, n):
-    """Decode steps of 2 .. 24 rows as ONE launch (up to 8 rows k_step2: the rows in pairs as two MFMA columns per block, an odd count
-    leaves the last pair half empty; 3 rows: k_step<true>, one chain of blocks per row; from 9 rows k_step4: four columns per block, the
-    last chain may hold 1 .. 3 rows) against the same steps on the launches (CV2_DECODE_SHARED)
+    """Decode steps of 2 .. 24 rows as ONE launch (up to 8 rows k_step_rows<2>: the rows in pairs as two MFMA columns per block, an odd count
+    leaves the last pair half empty; 3 rows: k_step<true>, one chain of blocks per row; from 9 rows k_step_rows<4>: four columns per block, the
+    last chain may hold 1 .. 3 rows -- 10: two, the chain's second O block finds no row) against the same steps on the launches (CV2_DECODE_SHARED)
     and the oracle: prompts of different lengths (every row has its own position, KV cache and attention-tile count), greedy and RAS.
     Per row every sum of the one-launch forms runs in the one-row kernel's order; the launches of up to 16 rows fold and normalise their
     operands the same way, those of 17 .. 32 rows (n = 22) from operands prepared once per row (another rounding of the normalised value):

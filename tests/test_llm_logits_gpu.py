@@ -81,12 +81,12 @@ def _lengths(n, base=12):
 
 
 def _one_launch(eng, n_rows, shared):
-    """the form cv2_llm_decode_ex / cv2_llm_decode_rows will take (csrc/llm.hip:2868, :2910; CH_ROWS_DEFAULT = 24)"""
+    """the form cv2_llm_decode_ex / cv2_llm_decode_rows will take (csrc/llm.hip: `one_launch` in cv2_llm_decode_ex and cv2_llm_decode_rows; CH_ROWS_DEFAULT = 24)"""
     return bool(eng.lib.cv2_llm_one_launch_step(eng.handle)) and not shared and not eng.chain_broken and n_rows <= 24
 
 
 def _greedy_ok(lg, tok):
-    """the id k_sample must draw in greedy forced-length mode: argmax over the ids below EOS, ties -> the lowest id (llm.hip:1636-1647)"""
+    """the id k_sample must draw in greedy forced-length mode: argmax over the ids below EOS, ties -> the lowest id (llm.hip: the masks at the top of k_sample)"""
     return int(lg[:EOS].argmax()) == tok
 
 
@@ -180,9 +180,10 @@ def _check(name, rig, xs, slots, steps=STEPS, shared=False, one_launch=True, mod
 
 
 # ---- every step form ------------------------------------------------------------------------------------------------------------
-# one launch: 1 row k_step, 3 rows k_step<true>, 2 / 5 / 8 rows k_step2 (5: a half-empty last pair), 9 / 13 / 16 / 24 rows k_step4
-# (9 and 13: a last chain of 1 row, 24: full, + 11: a last chain of 3); shared=True: the launches, 17 / 25 / 32 rows: prepared operands
-@pytest.mark.parametrize('n', [1, 2, 3, 5, 8, 9, 11, 13, 16, 24])
+# one launch: 1 row k_step, 3 rows k_step<true>, 2 / 5 / 6 / 8 rows k_step_rows<2> (5: a half-empty last pair, 6: three full pairs),
+# 9 / 10 / 11 / 13 / 16 / 24 rows k_step_rows<4> (9 and 13: a last chain of 1 row, 10: of 2 -- its second O block has no row and returns
+# early --, 11: of 3, 24: full); shared=True: the launches, 17 / 25 / 32 rows: prepared operands
+@pytest.mark.parametrize('n', [1, 2, 3, 5, 6, 8, 9, 10, 11, 13, 16, 24])
 def test_one_launch_forms(rig3, n):
     eng = rig3.eng
     xs = [_x(eng, 100 * n + r, ln) for r, ln in enumerate(_lengths(n))]
@@ -226,7 +227,7 @@ def test_one_row_step_behind_a_1500_token_prompt(dev, rig3):
 def test_long_context_engines(dev, rig3, max_pos, chain):
     """The engines of test_long_context_attention_splits: larger KV capacities change the launches' key splits (128-key splits with two
     wave groups at 1536, 512-key splits with four groups and a second round of tiles at 4400).  35 tiles x 2 kv heads are more than the
-    one-launch step carries (<= 64, csrc/llm.hip:2348): the 4400 engine has the launches only."""
+    one-launch step carries (<= 64, csrc/llm.hip: `use_chain` in cv2_llm_create): the 4400 engine has the launches only."""
     from cv2amd.llm import LLMEngine
     rig = Rig.__new__(Rig)
     rig.sdr, rig.sd64 = rig3.sdr, rig3.sd64

@@ -35,7 +35,7 @@ ROWS = tuple(int(v) for v in os.environ['CV2_SWEEP_ROWS'].split(',')) if os.envi
 for n in ROWS:
     slots = list(range(32 - n, 32))
     res = []
-    for shared in ((False, True) if n <= 24 else (False,)):         # <= 24 rows: the one-launch step (k_step2 pairs, k_step<true> at 3 rows, k_step4 from 9 rows), and the launches beside it
+    for shared in ((False, True) if n <= 24 else (False,)):         # <= 24 rows: the one-launch step (k_step_rows<2> pairs, k_step<true> at 3 rows, k_step_rows<4> from 9 rows), and the launches beside it
         reset(slots)
         res.append(timed(lambda k: eng.step_rows(slots, k, shared=shared)))
     print(f'rows {n:2d}: ' + (f'{res[0]:7.1f} (one launch)   {res[1]:7.1f} (launches)' if len(res) == 2 else f'{res[0]:7.1f} (launches)'), flush=True)
