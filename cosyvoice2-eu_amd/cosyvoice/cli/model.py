@@ -35,9 +35,10 @@ import numpy as np
 import torch
 
 from cv2amd.flow import FlowEngine
-from cv2amd.hift import HiftEngine, HiftPool
+from cv2amd.hift import HiftEngine, HiftPool, stretch_args, mel_stretch
 from cv2amd.llm import LLMEngine, MODE_RAS, MODE_GREEDY
 from cv2amd import lib as L
+from cv2amd import stretch as S
 
 
 class _FairLock:
@@ -147,6 +148,7 @@ class CosyVoice2Model:
         self.tts_speech_token_dict = {}
         self.llm_end_dict = {}
         self.hift_cache_dict = {}
+        self.stretch_dict = {}                 # uuid -> _Stretcher of a streaming call with speed != 1; created and dropped with hift_cache_dict[uuid]
         self._hift_pin, self._pin_rr = {}, -1  # uuid -> index of the HiftPool engine / HIP stream serving that call's chunks
         self.llm_stream = torch.cuda.Stream(self.device)   # (torch.cuda.Stream.priority_range() is (0, -1) here: no priority below the default exists)
         self.sampling_mode = MODE_RAS if sampling == 'ras' else MODE_GREEDY
@@ -244,7 +246,7 @@ class CosyVoice2Model:
         live = [i for i, m in enumerate(mels) if m is not None]
         if eng is None or self._noise_hook is not None or self._trace is not None or len(live) < 2:
             return None
-        cur, pre, out = torch.cuda.current_stream(), {}, [None] * len(grp)
+        cur, pre, out, jobs = torch.cuda.current_stream(), {}, [None] * len(grp), []
         for i in live:
             c, (mel, first) = grp[i], mels[i]
             assert c.offset * self.flow.token_mel_ratio >= first
@@ -254,8 +256,28 @@ class CosyVoice2Model:
             if cache is not None:
                 for t in cache.values():
                     t.record_stream(cur)
-                mel, cs = torch.concat([cache['mel'], mel], dim=2), cache['source']
+                cs = cache['source']
+            if c.speed != 1.0:                                                 # stretched below, straight behind the cached frames
+                jobs.append((i, self.stretch_dict[c.uuid], mel, cache, False))
+                pre[i] = (cache, None, cs)
+                continue
+            if cache is not None:
+                mel = torch.concat([cache['mel'], mel], dim=2)
             pre[i] = (cache, mel.contiguous(), cs)
+        if jobs:                                                               # every stretched chunk of the round in ONE launch
+            try:
+                bufs = self._stretch_chunks([j[1:] for j in jobs])
+            except Exception:                                                  # find the offender (nothing was committed): one by one
+                bufs = []
+                for j in jobs:
+                    try:
+                        bufs.append(self._stretch_chunks([j[1:]])[0])
+                    except Exception as e:
+                        grp[j[0]].exc = e
+                        bufs.append(None)
+            for j, b in zip(jobs, bufs):
+                pre[j[0]] = (pre[j[0]][0], b, pre[j[0]][2])
+            live = [i for i in live if pre[i][1] is not None]
         shapes = {}
         for i in live:
             _, mel, cs = pre[i]
@@ -276,9 +298,48 @@ class CosyVoice2Model:
                             grp[i].exc = e
         return out
 
+    class _Stretcher:
+        """A streaming call with speed != 1: the planner's counters (cv2amd/stretch.py) and the retained input frames on the device."""
+        __slots__ = ('state', 'tail')
+
+        def __init__(self, speed):
+            self.state, self.tail = S.StretchState(speed), None
+
+    def _stretch_chunks(self, jobs):
+        """The time-stretch of streaming calls with speed != 1, between the slice and the cache concat of
+        model.py:311-315.  jobs: [(stretcher, the chunk's new frames [1, 80, n], the call's hift cache or None, finalize)], one per
+        call.  Returns the vocoder inputs [1, 80, cached + emitted frames]: the kernel writes the emitted frames straight behind the
+        cached ones, all jobs in one launch.  The planner's integers are host arithmetic, the frames never leave the device.  The
+        stretchers advance only when the launch has succeeded."""
+        cur, args, bufs, plans = torch.cuda.current_stream(), [], [], []
+        for sx, mel, cache, finalize in jobs:
+            st, n_new = sx.state, mel.shape[2]
+            j0, n_emit, first_needed = S.plan(st, n_new, finalize)
+            nc = 0 if cache is None else cache['mel'].shape[2]
+            buf = mel.new_empty(1, mel.shape[1], nc + n_emit)
+            if nc:
+                buf[:, :, :nc] = cache['mel']
+            if sx.tail is not None:
+                sx.tail.record_stream(cur)                                     # (built on the stream of the call's previous round)
+            args.append(stretch_args(sx.tail, mel, buf, nc, st.first, st.consumed + n_new, j0, n_emit, st.r, finalize))
+            bufs.append(buf)
+            plans.append((n_new, n_emit, first_needed))
+        mel_stretch(args, rows=jobs[0][1].shape[1], device=self.device)
+        for (sx, mel, _c, finalize), (n_new, n_emit, first_needed) in zip(jobs, plans):
+            drop, nt = first_needed - sx.state.first, sx.state.n_tail          # frames of [tail, new] no later output frame reads
+            if finalize:
+                sx.tail = None
+            elif drop >= nt:
+                sx.tail = mel[:, :, drop - nt:].clone()
+            else:
+                sx.tail = torch.cat([sx.tail[:, :, drop:], mel], dim=2)
+            sx.state.commit(n_new, n_emit, first_needed, finalize)
+        return bufs
+
     def _mel2wav(self, tts_mel, token_offset, uuid, finalize, speed, hift=None, mel_first=0):
         """model.py:311-334: everything of token2wav after the flow (slice, mel / source / speech caches, HiFT, cross-fade).
-        mel_first: index of tts_mel's first frame in the mel flow.inference would have returned (cached chunks hold only the tail)."""
+        mel_first: index of tts_mel's first frame in the mel flow.inference would have returned (cached chunks hold only the tail).
+        A streaming call with speed != 1 has a stretcher (stretch_dict): its frames are time-stretched before they meet the caches."""
         hift = hift or self.hift
         flow_mel = tts_mel
         if mel_first and self._trace is not None:                              # tests slice the traced mel themselves: full-length view
@@ -286,16 +347,20 @@ class CosyVoice2Model:
         assert token_offset * self.flow.token_mel_ratio >= mel_first
         tts_mel = tts_mel[:, :, token_offset * self.flow.token_mel_ratio - mel_first:]
         cache = self.hift_cache_dict[uuid]
+        sx = self.stretch_dict.get(uuid) if speed != 1.0 else None
         if cache is not None:
             for t in cache.values():                                           # (the previous round may have built them on another stream of the pool)
                 t.record_stream(torch.cuda.current_stream())
-            tts_mel = torch.concat([cache['mel'], tts_mel], dim=2)
+            if sx is None:
+                tts_mel = torch.concat([cache['mel'], tts_mel], dim=2)
             hift_cache_source = cache['source']
         else:
             hift_cache_source = None
+        if sx is not None:
+            tts_mel = self._stretch_chunks([(sx, tts_mel, cache, finalize)])[0]
         noise = None
         if self._noise_hook is not None:
-            n_frames = int(tts_mel.shape[2] / speed) if (finalize and speed != 1.0) else tts_mel.shape[2]
+            n_frames = int(tts_mel.shape[2] / speed) if (finalize and speed != 1.0 and sx is None) else tts_mel.shape[2]
             noise = self._noise_hook(n_frames, uuid) if self._noise_hook_takes_uuid else self._noise_hook(n_frames)
         if self._trace is not None:
             self._trace.append((flow_mel.cpu(), token_offset, finalize, noise, uuid))
@@ -303,7 +368,7 @@ class CosyVoice2Model:
             tts_speech, tts_source = hift.inference(speech_feat=tts_mel.contiguous(), cache_source=hift_cache_source, noise=noise)
             tts_speech = self._chunk_post(uuid, cache, tts_mel, tts_speech, tts_source, hift)
         else:
-            if speed != 1.0:
+            if speed != 1.0 and sx is None:
                 assert cache is None, 'speed change only support non-stream inference mode'
                 tts_mel = hift.change_speed(tts_mel, speed)                     # F.interpolate(mode='linear') of model.py:329, on the device
             tts_speech, tts_source = hift.inference(speech_feat=tts_mel.contiguous(), cache_source=hift_cache_source, noise=noise)
@@ -313,7 +378,7 @@ class CosyVoice2Model:
 
     # ---- chunks of concurrent streams: one ragged flow batch for every chunk that is ready -------------------------------
     class _Chunk:
-        __slots__ = ('token', 'fpt', 'feat', 'femb', 'offset', 'uuid', 'stream', 'finalize', 'done', 'speech', 'exc', 'cap_hint', 'pkey', 'taken')
+        __slots__ = ('token', 'fpt', 'feat', 'femb', 'offset', 'uuid', 'stream', 'finalize', 'done', 'speech', 'exc', 'cap_hint', 'pkey', 'taken', 'speed')
 
     def _flow_cache_for(self, c):
         """The call's flow cache, large enough for this chunk.  Capacity: the caller's estimate of the utterance (frames), at least
@@ -424,7 +489,7 @@ class CosyVoice2Model:
                         mel, first = mel
                         with torch.cuda.stream(pool.streams[k]):
                             mel.record_stream(pool.streams[k])                 # produced on the main stream, consumed on the pinned one
-                            sp.append(self._mel2wav(mel, c.offset, c.uuid, c.finalize, 1.0, hift=pool.engines[k], mel_first=first))
+                            sp.append(self._mel2wav(mel, c.offset, c.uuid, c.finalize, c.speed, hift=pool.engines[k], mel_first=first))
                     except Exception as e:
                         c.exc = e
                         sp.append(None)
@@ -449,12 +514,12 @@ class CosyVoice2Model:
         self._pin_rr = (self._pin_rr + 1) % len(self.hift_pool.engines)
         return self._pin_rr
 
-    def _chunk_submit(self, token, fpt, feat, femb, offset, this_uuid, stream, finalize, cap_hint=None, pkey=None, first_slot=None):
+    def _chunk_submit(self, token, fpt, feat, femb, offset, this_uuid, stream, finalize, cap_hint=None, pkey=None, first_slot=None, speed=1.0):
         """token2wav for one chunk of a streaming call.  The chunk is queued; whoever gets the device next runs the flow over ALL
         queued chunks as one ragged batch (streams that share decode steps become ready together), then HiFT per chunk."""
         c = self._Chunk()
         c.token, c.fpt, c.feat, c.femb, c.offset, c.uuid, c.stream, c.finalize = token, fpt, feat, femb, offset, this_uuid, stream, finalize
-        c.done, c.speech, c.exc, c.cap_hint, c.pkey, c.taken = False, None, None, cap_hint, pkey, False
+        c.done, c.speech, c.exc, c.cap_hint, c.pkey, c.taken, c.speed = False, None, None, cap_hint, pkey, False, speed
         with self.lock:
             self._chunk_q.append(c)
         if self._sched_log is not None:
@@ -1036,14 +1101,14 @@ class CosyVoice2Model:
                     if len(toks) - token_offset < this_hop + la:
                         break
                     this_tok = torch.tensor(toks[:token_offset + this_hop + la], dtype=torch.int32).unsqueeze(0)
-                    speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, True, False)
+                    speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, True, False, speed=speed)
                     if call is not None:
                         call.first_done = True
                     token_offset += this_hop
                     yield {'tts_speech': speech}
                 pull(1 << 30)
                 this_tok = torch.tensor(list(toks), dtype=torch.int32).unsqueeze(0)
-                yield {'tts_speech': self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True)}
+                yield {'tts_speech': self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True, speed=speed)}
             else:
                 pull(1 << 30)
                 with self.run_lock:
@@ -1064,6 +1129,7 @@ class CosyVoice2Model:
                 self.tts_speech_token_dict.pop(this_uuid, None)
                 self.llm_end_dict.pop(this_uuid, None)
                 self.hift_cache_dict.pop(this_uuid, None)
+                self.stretch_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
 
@@ -1083,6 +1149,8 @@ class CosyVoice2Model:
         bistream = isinstance(text, Generator)                    # llm_job's bistream branch (model.py:120-128)
         if not vc and not bistream and not isinstance(text, torch.Tensor):
             raise TypeError('text must be a tensor of token ids or a generator of such tensors')
+        if stream is True and speed != 1.0:
+            S.check_speed(speed)               # streaming stretches within [0.5, 2] (cv2amd/stretch.py): refused before any work
         this_uuid = str(uuid.uuid1())
         # the current device is per thread and a new thread starts on device 0: callers run tts() from pool threads (the evaluation
         # harness, evaluation/cosyvoice_synthesizer.py:260) while the model may live on another GPU of the node (one rank per GPU)
@@ -1096,6 +1164,8 @@ class CosyVoice2Model:
         with self.lock:
             self.tts_speech_token_dict[this_uuid], self.llm_end_dict[this_uuid] = [], False
             self.hift_cache_dict[this_uuid] = None
+            if stream is True and speed != 1.0:
+                self.stretch_dict[this_uuid] = self._Stretcher(speed)
         if bistream and not vc:
             with self._bi_cv:                                                 # the hub waits (briefly) for calls on their way in before its first feed
                 self._bi_incoming += 1
@@ -1126,6 +1196,7 @@ class CosyVoice2Model:
                     self.tts_speech_token_dict.pop(this_uuid, None)
                     self.llm_end_dict.pop(this_uuid, None)
                     self.hift_cache_dict.pop(this_uuid, None)
+                    self.stretch_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
             return
@@ -1167,13 +1238,13 @@ class CosyVoice2Model:
                             self._llm_advance(need - len(toks))                # nothing in flight any more (ids above EOS are steps without a token)
                     if this_tok is not None:
                         speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, True, False, cap_hint, pkey,
-                                                    first_slot=slot if token_offset == 0 else None)
+                                                    first_slot=slot if token_offset == 0 else None, speed=speed)
                         token_offset += this_token_hop_len
                         yield {'tts_speech': speech}
                     if finished:
                         break
                 this_tok = torch.tensor(self.tts_speech_token_dict[this_uuid], dtype=torch.int32).unsqueeze(0)
-                speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True)
+                speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True, speed=speed)
                 yield {'tts_speech': speech}
             else:
                 self._llm_start(slot, text_d, ptext_d, lptok_d, force_len)
@@ -1203,8 +1274,11 @@ class CosyVoice2Model:
                 self._first_need.pop(slot, None)
             self._exit_shared(slot)
             with self.lock:
+                if self._token_log is not None:
+                    self._token_log[this_uuid] = list(self.tts_speech_token_dict.get(this_uuid, []))
                 self.tts_speech_token_dict.pop(this_uuid, None)
                 self.llm_end_dict.pop(this_uuid, None)
                 self.hift_cache_dict.pop(this_uuid, None)
+                self.stretch_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)

@@ -1292,6 +1292,123 @@ extern "C" int cv2_interp_linear(const float* in, float* out, int32_t rows, int3
     return 0;
 }
 
+// Streaming calls with speed != 1 (an extension of the reference): the time-stretch of the mel defined on the GLOBAL frame
+// index of the stream.  Output frame j reads the source position x = max(0, r (j + 0.5) - 0.5), evaluated in fp32 from the global j, so a value
+// never depends on where the chunk boundaries fell.  The source frames first .. n_avail - 1 come from two pieces: the tail the call retained
+// from earlier chunks and the frames the flow has just produced.  cv2amd/stretch.py evaluates the same fp32 expression on the host (which
+// frames can be emitted, which are retained), so the rounding is pinned down here instead of left to the compiler's contraction: x is ONE
+// fused multiply-add, r (j + 0.5) - 0.5 rounded once (j + 0.5 is exact below 2^23).  That is also what k_interp_linear compiles to and what
+// torch's CPU interpolation evaluates, so where N / speed is integral the stream's grid is F.interpolate's.  The blend itself is two rounded
+// products and a rounded sum, in k_interp_linear's expression order.
+__host__ __device__ __forceinline__ float stretch_pos(float r, int j) {
+    const float x = __builtin_fmaf(r, (float)j + 0.5f, -0.5f);
+    return x > 0.f ? x : 0.f;
+}
+
+// 16-byte loads where the source allows them: scalar up to the next 16-byte boundary, float4 from there, scalar for what is left
+__device__ __forceinline__ void stretch_stage(const float* __restrict__ src, int n, float* __restrict__ dst, int tid, int nthr) {
+    if (n <= 0) return;
+    const int head = min(n, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u)) & 15u) >> 2);
+    const int nv = (n - head) >> 2;
+    for (int i = tid; i < head; i += nthr) dst[i] = src[i];
+    const float4* v = reinterpret_cast<const float4*>(src + head);
+    for (int i = tid; i < nv; i += nthr) {
+        const float4 q = v[i];
+        float* d = dst + head + 4 * i;
+        d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
+    }
+    for (int i = head + 4 * nv + tid; i < n; i += nthr) dst[i] = src[i];
+}
+
+constexpr int ST_TJ = 256;                              // output frames per block
+constexpr int ST_ROWS = 4;                              // rows (mel channels) per block, 64 threads each
+constexpr int ST_SPAN = 4 * ST_TJ + 4;                  // source frames a tile can touch at r <= 4
+
+// grid (ceil(max n_emit / 256), ceil(rows / 4), streams).  tab: device table of per-stream arguments (one per blockIdx.z), or null: `one`.
+__global__ __launch_bounds__(256) void k_stretch(const cv2_stretch_args* __restrict__ tab, cv2_stretch_args one, int rows) {
+#pragma clang fp contract(off)
+    __shared__ float sm[ST_ROWS][ST_SPAN];
+    const cv2_stretch_args a = tab ? tab[blockIdx.z] : one;
+    const int t0 = blockIdx.x * ST_TJ;
+    if (t0 >= a.n_emit) return;                                               // (block-uniform)
+    const int nt = min(ST_TJ, a.n_emit - t0);
+    const int last = (a.n_final >= 0 ? a.n_final : a.n_avail) - 1;            // highest source frame there is
+    const int lo = min((int)stretch_pos(a.r, a.j0 + t0), last);
+    const int hi = min((int)stretch_pos(a.r, a.j0 + t0 + nt - 1) + 1, last);
+    const int span = min(hi - lo + 1, ST_SPAN);                               // (the entry point has checked r and the frame ranges)
+    const int lr = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.y * ST_ROWS + lr;
+    if (row < rows) {
+        // source frames lo .. lo + span - 1: [lo, cut) lies in the retained tail, [cut, ..) in the new frames
+        const int tail_end = a.first + a.n_tail;
+        const int n_from_tail = max(0, min(lo + span, tail_end) - lo);
+        if (n_from_tail > 0) stretch_stage(a.tail + (size_t)row * a.ld_tail + (lo - a.first), n_from_tail, sm[lr], lane, 64);
+        const int f0 = max(lo, tail_end);
+        stretch_stage(a.fresh + (size_t)row * a.ld_new + (f0 - tail_end), lo + span - f0, sm[lr] + (f0 - lo), lane, 64);
+    }
+    __syncthreads();
+    if (row >= rows) return;
+    float* out = a.dst + (size_t)row * a.ld_dst + a.dst_col + t0;
+    const int q = lane * 4;                                                   // four consecutive output frames per thread
+    if (q >= nt) return;
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const float x = stretch_pos(a.r, a.j0 + t0 + min(q + e, nt - 1));
+        const int i0 = min((int)x, last), i1 = min(i0 + 1, last);
+        const float w1 = x - (float)i0, w0 = 1.f - w1;
+        v[e] = w0 * sm[lr][i0 - lo] + w1 * sm[lr][i1 - lo];
+    }
+    if (q + 4 <= nt && (reinterpret_cast<uintptr_t>(out + q) & 15u) == 0) {
+        *reinterpret_cast<float4*>(out + q) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int e = 0; e < 4 && q + e < nt; e++) out[q + e] = v[e];
+    }
+}
+
+static int stretch_check(const cv2_stretch_args& a, int z) {
+    CV2_CHECK(a.dst && a.ld_dst >= 1 && a.dst_col >= 0, "cv2_mel_stretch: stream %d: bad destination", z);
+    CV2_CHECK(a.r >= 0.25f && a.r <= 4.f, "cv2_mel_stretch: stream %d: r = %g outside [0.25, 4]", z, (double)a.r);
+    CV2_CHECK(a.first >= 0 && a.n_tail >= 0 && a.n_avail >= a.first + a.n_tail && a.n_avail >= 1, "cv2_mel_stretch: stream %d: bad frame counts", z);
+    CV2_CHECK(a.n_final == -1 || a.n_final == a.n_avail, "cv2_mel_stretch: stream %d: n_final %d is neither -1 nor n_available %d", z, a.n_final, a.n_avail);
+    CV2_CHECK(a.j0 >= 0 && a.n_emit >= 0 && (long)a.j0 + a.n_emit <= (1l << 23), "cv2_mel_stretch: stream %d: bad output range", z);
+    CV2_CHECK(a.dst_col + a.n_emit <= a.ld_dst, "cv2_mel_stretch: stream %d: %d frames at column %d do not fit a row of %d", z, a.n_emit, a.dst_col, a.ld_dst);
+    const int n_new = a.n_avail - a.first - a.n_tail;
+    CV2_CHECK((a.n_tail == 0 || (a.tail && a.ld_tail >= a.n_tail)) && (n_new == 0 || (a.fresh && a.ld_new >= n_new)), "cv2_mel_stretch: stream %d: bad source", z);
+    if (a.n_emit > 0) {
+        // every frame the outputs read is one of first .. n_available - 1 (at the final chunk the right neighbour is clamped there instead)
+        const int i_lo = (int)stretch_pos(a.r, a.j0), i_hi = (int)stretch_pos(a.r, a.j0 + a.n_emit - 1);
+        CV2_CHECK(i_lo >= a.first, "cv2_mel_stretch: stream %d: output %d needs frame %d, retained from %d on", z, a.j0, i_lo, a.first);
+        CV2_CHECK(a.n_final >= 0 ? i_hi <= a.n_avail - 1 : i_hi + 1 <= a.n_avail - 1, "cv2_mel_stretch: stream %d: output %d needs a frame beyond the %d available", z,
+                  a.j0 + a.n_emit - 1, a.n_avail);
+    }
+    return 0;
+}
+
+extern "C" int cv2_mel_stretch(const cv2_stretch_args* a, int32_t rows, void* stream) {
+    CV2_CHECK(a && rows >= 1 && rows <= 4 * 65535, "cv2_mel_stretch: bad argument");
+    if (stretch_check(*a, 0)) return -1;
+    if (a->n_emit == 0) return 0;
+    hipLaunchKernelGGL(k_stretch, dim3((a->n_emit + ST_TJ - 1) / ST_TJ, (rows + ST_ROWS - 1) / ST_ROWS, 1), dim3(256), 0, (hipStream_t)stream,
+                       (const cv2_stretch_args*)nullptr, *a, (int)rows);
+    CV2_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cv2_mel_stretch_batch(const cv2_stretch_args* args, const cv2_stretch_args* table_dev, int32_t n, int32_t rows, void* stream) {
+    CV2_CHECK(args && table_dev && n >= 1 && n <= 65535 && rows >= 1 && rows <= 4 * 65535, "cv2_mel_stretch_batch: bad argument");
+    int max_emit = 0;
+    for (int z = 0; z < n; z++) {
+        if (stretch_check(args[z], z)) return -1;
+        max_emit = args[z].n_emit > max_emit ? args[z].n_emit : max_emit;
+    }
+    if (max_emit == 0) return 0;
+    hipLaunchKernelGGL(k_stretch, dim3((max_emit + ST_TJ - 1) / ST_TJ, (rows + ST_ROWS - 1) / ST_ROWS, n), dim3(256), 0, (hipStream_t)stream,
+                       table_dev, args[0], (int)rows);
+    CV2_LAUNCH_CHECK();
+    return 0;
+}
+
 // ------------------------------------------------------------------ test hook: the conv pre-activations (Snake / leaky ReLU) as k_conv evaluates them
 __global__ void k_dbg_pre(const float* x, float* out, int n, int pre, float alpha, float slope) {
     const int i = blockIdx.x * 256 + threadIdx.x;

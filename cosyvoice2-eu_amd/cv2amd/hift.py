@@ -32,6 +32,12 @@ class HiftDims(C.Structure):
     _fields_ = [('max_frames', C.c_int32), ('lanes', C.c_int32)]
 
 
+class StretchArgs(C.Structure):
+    """cv2_stretch_args (72 bytes): one stream's chunk of the streaming time-stretch."""
+    _fields_ = [('tail', C.c_void_p), ('fresh', C.c_void_p), ('dst', C.c_void_p)] + [(n, C.c_int32) for n in
+               ('ld_tail', 'ld_new', 'ld_dst', 'dst_col', 'first', 'n_tail', 'n_avail', 'j0', 'n_emit', 'n_final')] + [('r', C.c_float), ('reserved', C.c_int32)]
+
+
 def _bind(lib):
     if getattr(lib, '_hift_bound', False):
         return
@@ -45,6 +51,8 @@ def _bind(lib):
     lib.cv2_hift_inference_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]
     lib.cv2_interp_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.cv2_mel_stretch.argtypes = [C.POINTER(StretchArgs), C.c_int32, C.c_void_p]
+    lib.cv2_mel_stretch_batch.argtypes = [C.POINTER(StretchArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib._hift_bound = True
 
 
@@ -98,6 +106,45 @@ def polyphase(wt, u, pad):
             if 0 <= kk < k:
                 w[r * co:(r + 1) * co, :, j] = wt[:, :, kk].t()
     return w
+
+
+def _rows_ld(t):
+    """(pointer, leading dimension) of a [1, rows, n] fp32 device tensor whose time axis is contiguous (a time slice of a mel is)."""
+    assert t.dim() == 3 and t.shape[0] == 1 and t.dtype == torch.float32 and (t.shape[2] <= 1 or t.stride(2) == 1)
+    return t.data_ptr(), max(t.stride(1), t.shape[2], 1)
+
+
+def stretch_args(tail, fresh, dst, dst_col, first, n_avail, j0, n_emit, r, final):
+    """One stream's record for mel_stretch: tail / fresh [1, rows, n] (None or empty: no such frames) are the source frames
+    first .. n_avail - 1, dst [1, rows, >= dst_col + n_emit] receives the output frames j0 .. j0 + n_emit - 1 from column dst_col
+    on.  The integers come from cv2amd.stretch.plan; the frames stay on the device."""
+    a = StretchArgs()
+    a.n_tail = 0 if tail is None else tail.shape[2]
+    if a.n_tail:
+        a.tail, a.ld_tail = _rows_ld(tail)
+    if fresh is not None and fresh.shape[2]:
+        a.fresh, a.ld_new = _rows_ld(fresh)
+        assert fresh.shape[2] == n_avail - first - a.n_tail
+    a.dst, a.ld_dst = _rows_ld(dst)
+    a.dst_col, a.first, a.n_avail, a.j0, a.n_emit, a.n_final, a.r = dst_col, first, n_avail, j0, n_emit, n_avail if final else -1, float(r)
+    return a
+
+
+def mel_stretch(args, rows=80, device=None):
+    """The streaming time-stretch of one or several streams on the current HIP stream: cv2_mel_stretch, or ONE
+    cv2_mel_stretch_batch launch (gridDim.z = streams) fed by a device table of the records.  The caller keeps the tensors behind
+    the records alive.  There is no CPU fallback."""
+    lib = L.lib()
+    _bind(lib)
+    if len(args) == 1:
+        L.check(lib.cv2_mel_stretch(C.byref(args[0]), rows, L.stream_ptr()))
+        return
+    n = len(args)
+    arr = (StretchArgs * n)(*args)
+    host = torch.empty(n * C.sizeof(StretchArgs), dtype=torch.uint8, pin_memory=True)
+    C.memmove(host.data_ptr(), arr, n * C.sizeof(StretchArgs))
+    table = host.to(device or torch.device('cuda', torch.cuda.current_device()), non_blocking=True)     # (pinned: ordered on the stream, the host goes on)
+    L.check(lib.cv2_mel_stretch_batch(arr, table.data_ptr(), n, rows, L.stream_ptr()))
 
 
 class HiftEngine:

@@ -396,6 +396,29 @@ int cv2_fade_in_out(float* fade_in, const float* old_tail, const float* window, 
  * (torch.nn.functional.interpolate(mode='linear'), align_corners False); in [rows][n_in], out [rows][n_out], fp32 device. */
 int cv2_interp_linear(const float* in, float* out, int32_t rows, int32_t n_in, int32_t n_out, void* stream);
 
+/* Streaming calls with speed != 1 (an extension: the reference asserts, cli/model.py:328): a time-stretch of the mel defined on the GLOBAL
+ * frame index of the stream, so that chunk boundaries cannot change a value.  m[0 .. N) are the frames a streaming call hands to the vocoder
+ * stage, in order; with r = (float)speed output frame j is w0 m[i0] + w1 m[i1], x = max(0, fma(r, j + 0.5, -0.5)) in fp32 from the global j (one
+ * rounding), i0 = floor(x), i1 = min(i0 + 1, n_final - 1), w1 = x - i0, w0 = 1 - w1.  One call emits the
+ * frames j0 .. j0 + n_emit - 1 of one stream; which frames can be emitted and which source frames stay is planned on the host
+ * (cv2amd/stretch.py evaluates the same fp32 expression).  The source frames first .. n_available - 1 are given as two pieces: `tail`
+ * (n_tail frames from global index `first` on, retained from earlier chunks) and `fresh` (the n_available - first - n_tail new frames);
+ * both [rows][ld] fp32, time contiguous.  Frame j lands at dst[row * ld_dst + dst_col + (j - j0)]: straight behind the cached mel frames of
+ * the vocoder's input.  n_final: -1 while more frames will come (then every i0 + 1 <= n_available - 1 is required), else = n_available.
+ * 0.25 <= r <= 4; j0 + n_emit <= 2^23.  Adding these entry points changed no struct and no signature: CV2_ABI_VERSION stays. */
+typedef struct {
+    const float* tail; const float* fresh; float* dst;
+    int32_t ld_tail, ld_new, ld_dst, dst_col;
+    int32_t first, n_tail, n_avail;
+    int32_t j0, n_emit, n_final;
+    float r;
+    int32_t reserved;
+} cv2_stretch_args;                                                  /* 72 bytes */
+int cv2_mel_stretch(const cv2_stretch_args* a, int32_t rows, void* stream);       /* a: host */
+/* n streams as ONE launch (gridDim.z = n): `args` are the n records on the host (checked here), `table_dev` the same n records in device
+ * memory, uploaded by the caller ahead of this call on `stream` -- the kernel reads its stream's record from there. */
+int cv2_mel_stretch_batch(const cv2_stretch_args* args, const cv2_stretch_args* table_dev, int32_t n, int32_t rows, void* stream);
+
 /* =====================================================================================================================
  * Prompt features (the extractor that feeds this path): replaces the reference's
  *   feat_extractor = matcha.utils.audio.mel_spectrogram(n_fft 1920, num_mels 80, sampling_rate 24000, hop_size 480, win_size 1920,

@@ -1,6 +1,8 @@
 """First-chunk latency of N concurrent streaming calls on ONE model (BASELINE config 5: streaming, B = 8):
-python tools/bench_streams.py [streams] [rounds] [--stagger MS] [--fresh-threads] [--trace].  Each round starts N calls at once (or within MS
-milliseconds of each other); reports p50 / max of the time from a call to its first chunk."""
+python tools/bench_streams.py [streams] [rounds] [--stagger MS] [--speed S] [--fresh-threads] [--trace].  Each round starts N calls at once (or within MS
+milliseconds of each other); reports p50 / max of the time from a call to its first chunk and the p50 gap between a stream's chunks.
+--speed S: every call streams at that speed (the mel time-stretch of DESIGN section 1); the line then also says how the non-final chunks
+reached the vocoder: through inference_batch (chunks of one shape in one set of launches) or singly."""
 import os, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'cosyvoice2-eu_amd'))
@@ -8,7 +10,7 @@ import torch
 from cv2amd import synth
 from cosyvoice.cli.model import CosyVoice2Model
 
-_a = [x for i, x in enumerate(sys.argv[1:]) if not x.startswith('--') and sys.argv[i] != '--stagger']
+_a = [x for i, x in enumerate(sys.argv[1:]) if not x.startswith('--') and sys.argv[i] not in ('--stagger', '--speed')]
 N = int(_a[0]) if len(_a) > 0 else 8
 R = int(_a[1]) if len(_a) > 1 else 4
 m = CosyVoice2Model(synth.make_llm(), synth.make_flow(), synth.make_hift(), max_text=128, max_prompt_tokens=320, max_new_tokens=1100,
@@ -21,6 +23,20 @@ kw = dict(text=inp['text'], prompt_text=inp['prompt_text'], llm_prompt_speech_to
 
 
 import random
+SPEED = float(sys.argv[sys.argv.index('--speed') + 1]) if '--speed' in sys.argv else 1.0
+_how = {'batched': 0, 'single': 0}               # non-final chunks of shared rounds: vocoder calls through inference_batch / one by one
+if m.hift_pool.batch_engine is not None:
+    _ib, _one = m.hift_pool.batch_engine.inference_batch, m.hift.inference
+
+    def _count_batch(mels, *a, **k):
+        _how['batched'] += len(mels)
+        return _ib(mels, *a, **k)
+
+    def _count_one(*a, **k):
+        if 'cache_source' in k and 'noise' not in k:             # (the call form of _chunks_batched_hift's single branch)
+            _how['single'] += 1
+        return _one(*a, **k)
+    m.hift_pool.batch_engine.inference_batch, m.hift.inference = _count_batch, _count_one
 STAGGER = float(sys.argv[sys.argv.index('--stagger') + 1]) if '--stagger' in sys.argv else 0.0      # --stagger MS: random start offsets
 _rng = random.Random(1986)
 POOL = '--fresh-threads' not in sys.argv       # callers are the persistent workers of a server's pool (default); --fresh-threads: new threads per
@@ -52,7 +68,7 @@ class _Pool:
 
 def run(n):
     global _pool
-    first, total = [None] * n, [0.0] * n
+    first, total, gaps = [None] * n, [0.0] * n, []
     if POOL and _pool is None:
         _pool = _Pool(N)
     t0 = time.perf_counter()
@@ -62,9 +78,14 @@ def run(n):
         if STAGGER > 0:                            # calls that do NOT start together: each waits a random 0 .. STAGGER ms first
             time.sleep(_rng.random() * STAGGER * 1e-3)
             t_call = time.perf_counter()
-        for out in m.tts(**kw, stream=True):
+        t_prev = None
+        for out in m.tts(**kw, stream=True, speed=SPEED):
+            now = time.perf_counter()
             if first[i] is None:
-                first[i] = time.perf_counter() - t_call
+                first[i] = now - t_call
+            else:
+                gaps.append(now - t_prev)
+            t_prev = now
             total[i] += out['tts_speech'].shape[1] / 24000.0
     if POOL:
         _pool.run(work, n)
@@ -72,7 +93,7 @@ def run(n):
         ths = [threading.Thread(target=work, args=(i,)) for i in range(n)]
         [t.start() for t in ths]
         [t.join() for t in ths]
-    return first, sum(total), time.perf_counter() - t0
+    return first, sum(total), time.perf_counter() - t0, gaps
 
 
 run(1); run(N)                                   # warm-up (graphs for 1..N slots)
@@ -82,17 +103,20 @@ if '--trace' in sys.argv:                        # one round of N streams with a
             m._prompt_caches.clear()
         m._sched_log = []
         t0 = time.perf_counter()
-        f, audio, dt = run(N)
+        f, audio, dt, _g = run(N)
         log, m._sched_log = m._sched_log, None
         print(f'--- {N} streams, {"new" if new_prompt else "served"} prompt: first chunks (ms) {sorted(round(x * 1e3) for x in f)}')
         for t, kind, info in sorted(log):
             print(f'{(t - t0) * 1e3:8.2f} ms  {kind:6s} {info}')
     sys.exit(0)
 for n in (1, N):
-    firsts = []
+    firsts, gaps = [], []
+    _how['batched'] = _how['single'] = 0
     for _ in range(R):
-        f, audio, dt = run(n)
+        f, audio, dt, g = run(n)
         firsts += f
-    firsts.sort()
-    print(f'{n} concurrent stream(s): first chunk p50 {firsts[len(firsts) // 2] * 1e3:.1f} ms, max {firsts[-1] * 1e3:.1f} ms; '
-          f'last round {audio:.1f} s of audio in {dt:.2f} s = {audio / dt:.1f} audio-s/s')
+        gaps += g
+    firsts.sort(); gaps.sort()
+    print(f'speed {SPEED}: {n} concurrent stream(s): first chunk p50 {firsts[len(firsts) // 2] * 1e3:.1f} ms, max {firsts[-1] * 1e3:.1f} ms; '
+          f'chunk gap p50 {gaps[len(gaps) // 2] * 1e3 if gaps else 0.0:.1f} ms; last round {audio:.1f} s of audio in {dt:.2f} s = {audio / dt:.1f} audio-s/s; '
+          f'non-final chunks in shared rounds: {_how["batched"]} through inference_batch, {_how["single"]} singly', flush=True)
