@@ -16,13 +16,20 @@ from cosyvoice.cli.model import CosyVoice2Model
 
 class CosyVoice2:
     def __init__(self, model_dir, load_jit=False, load_trt=False, load_vllm=False, fp16=False, trt_concurrent=1, setting='original',
-                 llm_run_id=None, flow_run_id=None, hifigan_run_id=None, final=False, backbone=None, frontend=None, state_dicts=None):
+                 llm_run_id=None, flow_run_id=None, hifigan_run_id=None, final=False, backbone=None, frontend=None, state_dicts=None,
+                 output_sample_rate=None, output_pcm16=False):
         """model_dir: directory with llm/flow/hift checkpoints (+ tokenizer and ONNX frontend models).
         Extra keyword-only hooks of this build: `frontend` (object with the CosyVoiceFrontEnd interface) and `state_dicts`
-        (llm, flow, hift) to construct the model without files (synthetic weights, tests)."""
+        (llm, flow, hift) to construct the model without files (synthetic weights, tests); `output_sample_rate` (8000, 16000, 22050,
+        24000, 32000, 44100 or 48000) and `output_pcm16`: every inference_* call yields its audio at that rate and / or as int16 PCM,
+        converted on the device.  `.sample_rate` then reports the output rate, `.model_sample_rate` the model's."""
+        if output_sample_rate is not None:
+            from cv2amd import outrate
+            outrate.check_rate(output_sample_rate)                          # refused before anything is loaded
+        self.output_sample_rate, self.output_pcm16 = output_sample_rate, bool(output_pcm16)
         self.model_dir = model_dir
         self.fp16 = fp16
-        self.sample_rate = 24000                                            # conf/cosyvoice2.yaml:8
+        self.model_sample_rate = 24000                                      # conf/cosyvoice2.yaml:8; what the frontends receive as resample_rate
         if load_jit or load_trt or load_vllm:
             logging.warning('load_jit / load_trt / load_vllm are NVIDIA-path accelerators of the reference; ignored on MI355X')
         if state_dicts is None and not os.path.exists(model_dir):
@@ -52,7 +59,7 @@ class CosyVoice2:
                 overrides['qwen_pretrain_path'] = qwen
                 logging.info('Using LLM backbone: {}'.format(qwen))
             config = Config.from_file(hyper_yaml_path, overrides)
-            self.sample_rate = config.sample_rate
+            self.model_sample_rate = config.sample_rate
         self.config = config
         # checkpoint selection, cli/cosyvoice.py:240-265
         if final:
@@ -88,12 +95,29 @@ class CosyVoice2:
                 logging.warning('prompt frontend unavailable (%s); only pre-extracted prompts (add_zero_shot_spk / spk2info) will work', e)
                 self.frontend = PrecomputedFrontEnd(lambda t: (_ for _ in ()).throw(FrontEndUnavailable('no tokenizer')))
 
+    @property
+    def sample_rate(self):
+        """the rate of the yielded audio (callers write files with it): the output rate when one was asked for, else the model's"""
+        return self.output_sample_rate if self.output_sample_rate is not None else self.model_sample_rate
+
+    def output(self, sample_rate=None, pcm16=None):
+        """A view of this object (same model, same frontend) that yields at another output rate / format: what a server uses for a
+        request that asks for its own rate.  None keeps this object's setting."""
+        import copy
+        if sample_rate is not None:
+            from cv2amd import outrate
+            outrate.check_rate(sample_rate)
+        view = copy.copy(self)
+        view.output_sample_rate = self.output_sample_rate if sample_rate is None else sample_rate
+        view.output_pcm16 = self.output_pcm16 if pcm16 is None else bool(pcm16)
+        return view
+
     def list_available_spks(self):
         return list(self.frontend.spk2info.keys())
 
     def add_zero_shot_spk(self, prompt_text, prompt_speech_16k, zero_shot_spk_id):
         assert zero_shot_spk_id != '', 'do not use empty zero_shot_spk_id'
-        model_input = self.frontend.frontend_zero_shot('', prompt_text, prompt_speech_16k, self.sample_rate, '')
+        model_input = self.frontend.frontend_zero_shot('', prompt_text, prompt_speech_16k, self.model_sample_rate, '')
         del model_input['text']
         del model_input['text_len']
         self.frontend.spk2info[zero_shot_spk_id] = model_input
@@ -105,7 +129,10 @@ class CosyVoice2:
     def _run(self, model_input, stream, speed, label):
         start_time = time.time()
         logging.info('synthesis text {}'.format(label))
-        for model_output in self.model.tts(**model_input, stream=stream, speed=speed):
+        extra = {}
+        if self.output_sample_rate is not None or self.output_pcm16:
+            extra = dict(output_sample_rate=self.output_sample_rate, pcm16=self.output_pcm16)
+        for model_output in self.model.tts(**model_input, stream=stream, speed=speed, **extra):
             speech_len = model_output['tts_speech'].shape[1] / self.sample_rate
             logging.info('yield speech len {}, rtf {}'.format(speech_len, (time.time() - start_time) / speech_len))
             yield model_output
@@ -123,17 +150,17 @@ class CosyVoice2:
         for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
             if isinstance(i, str) and len(i) < 0.5 * len(prompt_text):
                 logging.warning('synthesis text {} too short than prompt text {}, this may lead to bad performance'.format(i, prompt_text))
-            model_input = self.frontend.frontend_zero_shot(i, prompt_text, prompt_speech_16k, self.sample_rate, zero_shot_spk_id)
+            model_input = self.frontend.frontend_zero_shot(i, prompt_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
             yield from self._run(model_input, stream, speed, i)
 
     def inference_cross_lingual(self, tts_text, prompt_speech_16k, zero_shot_spk_id='', stream=False, speed=1.0, text_frontend=True):
         for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
-            model_input = self.frontend.frontend_cross_lingual(i, prompt_speech_16k, self.sample_rate, zero_shot_spk_id)
+            model_input = self.frontend.frontend_cross_lingual(i, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
             yield from self._run(model_input, stream, speed, i)
 
     def inference_vc(self, source_speech_16k, prompt_speech_16k, stream=False, speed=1.0):
         """cli/cosyvoice.py:132-139: voice conversion = the source utterance's speech tokens through flow + HiFT with the prompt's voice."""
-        model_input = self.frontend.frontend_vc(source_speech_16k, prompt_speech_16k, self.sample_rate)
+        model_input = self.frontend.frontend_vc(source_speech_16k, prompt_speech_16k, self.model_sample_rate)
         yield from self._run(model_input, stream, speed, 'vc')
 
     def inference_instruct(self, *args, **kwargs):
@@ -142,5 +169,5 @@ class CosyVoice2:
     def inference_instruct2(self, tts_text, instruct_text, prompt_speech_16k, zero_shot_spk_id='', stream=False, speed=1.0, text_frontend=True):
         """cli/cosyvoice.py:284-295: same three stages, the instruction rides in the prompt-text slot."""
         for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
-            model_input = self.frontend.frontend_instruct2(i, instruct_text, prompt_speech_16k, self.sample_rate, zero_shot_spk_id)
+            model_input = self.frontend.frontend_instruct2(i, instruct_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
             yield from self._run(model_input, stream, speed, i)

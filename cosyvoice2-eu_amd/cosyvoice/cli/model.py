@@ -39,6 +39,7 @@ from cv2amd.hift import HiftEngine, HiftPool, stretch_args, mel_stretch
 from cv2amd.llm import LLMEngine, MODE_RAS, MODE_GREEDY
 from cv2amd import lib as L
 from cv2amd import stretch as S
+from cv2amd import outrate as O
 
 
 class _FairLock:
@@ -149,6 +150,7 @@ class CosyVoice2Model:
         self.llm_end_dict = {}
         self.hift_cache_dict = {}
         self.stretch_dict = {}                 # uuid -> _Stretcher of a streaming call with speed != 1; created and dropped with hift_cache_dict[uuid]
+        self.out_dict = {}                     # uuid -> _Out of a call with output_sample_rate / pcm16; created and dropped with hift_cache_dict[uuid]
         self._hift_pin, self._pin_rr = {}, -1  # uuid -> index of the HiftPool engine / HIP stream serving that call's chunks
         self.llm_stream = torch.cuda.Stream(self.device)   # (torch.cuda.Stream.priority_range() is (0, -1) here: no priority below the default exists)
         self.sampling_mode = MODE_RAS if sampling == 'ras' else MODE_GREEDY
@@ -336,6 +338,68 @@ class CosyVoice2Model:
             sx.state.commit(n_new, n_emit, first_needed, finalize)
         return bufs
 
+    class _Out:
+        """A call with output_sample_rate / pcm16: the planner's counters (cv2amd/outrate.py), the filter table of its rate and the
+        retained source samples on the device."""
+        __slots__ = ('state', 'tail', 'pcm16', 'table')
+
+        def __init__(self, rate, pcm16, device):
+            self.state, self.tail, self.pcm16 = O.OutState(rate), None, bool(pcm16)
+            self.table = O.kernel_table(device, rate)
+
+    def _out_convert(self, jobs):
+        """The output conversion of what _mel2wav / token2wav produced, after fade and trim and before the
+        device-to-host copy.  jobs: [(_Out, waveform [1, n] fp32 on the device, finalize)], one per call; returns the [1, n_emit]
+        float32 / int16 device tensors, all jobs in ONE launch on the current stream.  The planner's integers are host arithmetic, the
+        samples never leave the device.  The states advance only when the launch has succeeded."""
+        cur, args, dsts, plans = torch.cuda.current_stream(), [], [], []
+        for ox, wav, finalize in jobs:
+            st, x = ox.state, wav.reshape(-1)
+            o0, n_emit, first_needed = O.plan(st, x.numel(), finalize)
+            dst = torch.empty(n_emit, dtype=torch.int16 if ox.pcm16 else torch.float32, device=wav.device)
+            if ox.tail is not None:
+                ox.tail.record_stream(cur)                                     # (built on the stream of the call's previous round)
+            args.append(O.out_args(st, ox.tail, x, dst, o0, n_emit, finalize, ox.table))
+            dsts.append(dst)
+            plans.append((x, n_emit, first_needed))
+        O.out_resample(args, device=self.device)
+        for (ox, _w, finalize), (x, n_emit, first_needed) in zip(jobs, plans):
+            drop, nt = first_needed - ox.state.first, ox.state.n_tail          # samples of [tail, new] no later output reads
+            if finalize or first_needed == ox.state.consumed + x.numel():
+                ox.tail = None
+            elif drop >= nt:
+                ox.tail = x[drop - nt:].clone()
+            else:
+                ox.tail = torch.cat([ox.tail[drop:], x])
+            ox.state.commit(x.numel(), n_emit, first_needed, finalize)
+        return [d.unsqueeze(0) for d in dsts]
+
+    def _out_one(self, uuid, wav):
+        """the one waveform of a non-streaming call on its way out"""
+        ox = self.out_dict.get(uuid)
+        return wav if ox is None else self._out_convert([(ox, wav, True)])[0]
+
+    def _out_chunks(self, grp, ws):
+        """The chunks of one round on their way out: those of calls with an output conversion (out_dict) are converted, all in ONE
+        cv2_out_resample_batch launch; the others are handed on as they are."""
+        idx = [i for i, (c, w) in enumerate(zip(grp, ws)) if w is not None and c.uuid in self.out_dict]
+        if not idx:
+            return ws
+        ws, jobs = list(ws), [(self.out_dict[grp[i].uuid], ws[i], grp[i].finalize) for i in idx]
+        try:
+            res = self._out_convert(jobs)
+        except Exception:                                                      # find the offender (nothing was committed): one by one
+            res = []
+            for i, j in zip(idx, jobs):
+                try:
+                    res.append(self._out_convert([j])[0])
+                except Exception as e:
+                    grp[i].exc = e
+                    res.append(None)
+        for i, r in zip(idx, res):
+            ws[i] = r
+        return ws
+
     def _mel2wav(self, tts_mel, token_offset, uuid, finalize, speed, hift=None, mel_first=0):
         """model.py:311-334: everything of token2wav after the flow (slice, mel / source / speech caches, HiFT, cross-fade).
         mel_first: index of tts_mel's first frame in the mel flow.inference would have returned (cached chunks hold only the tail).
@@ -473,7 +537,7 @@ class CosyVoice2Model:
                 pool, main, sp = self.hift_pool, torch.cuda.current_stream(), []
                 batched = self._chunks_batched_hift(grp, mels) if (key[0] and not key[1]) else None
                 if batched is not None:                                        # one vocoder call per chunk shape instead of one per chunk
-                    for c, w in zip(grp, batched):
+                    for c, w in zip(grp, self._out_chunks(grp, batched)):
                         if w is not None:
                             c.speech = w.cpu()
                     continue
@@ -495,9 +559,11 @@ class CosyVoice2Model:
                         sp.append(None)
                 for k in used:
                     main.wait_stream(pool.streams[k])
-                for c, w in zip(grp, sp):
+                for w in sp:
                     if w is not None:
                         w.record_stream(main)
+                for c, w in zip(grp, self._out_chunks(grp, sp)):
+                    if w is not None:
                         c.speech = w.cpu()
         except BaseException as e:                                            # not attributable to one chunk: every waiting stream sees it
             for c in batch:
@@ -804,7 +870,7 @@ class CosyVoice2Model:
 
     # ---- coalesced non-streaming calls ---------------------------------------------------------------------------
     class _Pending:
-        __slots__ = ('text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'speed', 'uuid', 'done', 'speech', 'exc', 'force_len', 'dev_out')
+        __slots__ = ('text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'speed', 'uuid', 'done', 'speech', 'exc', 'force_len', 'dev_out', 'out')
 
     def _run_batch(self, batch):
         """llm_job + token2wav(finalize=True) of model.py:118-139,300-334 for several queued calls at once.  Only the caller whose
@@ -846,7 +912,23 @@ class CosyVoice2Model:
                 gm.append(m.contiguous())
             outs = self.hift_pool.inference_many(gm) if gm else []
             torch.cuda.synchronize(self.device)
-            for (p, _), (wav, _s) in zip(good, outs):
+            conv = {}
+            cj = [(k, (p.out, wav, True)) for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)) if p.out is not None]
+            if cj:                                                            # every converted waveform of the batch in ONE launch (ragged lengths)
+                try:
+                    conv = dict(zip([k for k, _ in cj], self._out_convert([j for _, j in cj])))
+                except Exception:                                              # find the offender (nothing was committed): one by one
+                    for k, j in cj:
+                        try:
+                            conv[k] = self._out_convert([j])[0]
+                        except Exception as e:
+                            good[k][0].exc = e
+                torch.cuda.synchronize(self.device)
+            for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)):
+                if p.out is not None:
+                    if k in conv:
+                        p.speech = conv[k] if p.dev_out else conv[k].cpu()
+                    continue
                 p.speech = wav.clone() if p.dev_out else wav.cpu()      # (device_output: the waveform stays in HBM for a device-side consumer)
         except BaseException as e:                                            # not attributable to one request
             for p in batch:
@@ -1113,7 +1195,7 @@ class CosyVoice2Model:
                 pull(1 << 30)
                 with self.run_lock:
                     this_tok = torch.tensor(list(toks), dtype=torch.int32).unsqueeze(0)
-                    speech = self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed).cpu()
+                    speech = self._out_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed)).cpu()
                 yield {'tts_speech': speech}
         finally:
             if incoming:
@@ -1130,6 +1212,7 @@ class CosyVoice2Model:
                 self.llm_end_dict.pop(this_uuid, None)
                 self.hift_cache_dict.pop(this_uuid, None)
                 self.stretch_dict.pop(this_uuid, None)
+                self.out_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
 
@@ -1139,11 +1222,14 @@ class CosyVoice2Model:
             llm_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             flow_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             prompt_speech_feat=torch.zeros(1, 0, 80), source_speech_token=torch.zeros(1, 0, dtype=torch.int32), stream=False, speed=1.0,
-            force_len=None, device_output=False, **kwargs):
+            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, **kwargs):
         """force_len (an extension; the reference swallows unknown keywords in **kwargs): synthetic-weights mode of SURVEY.md §8(d) —
         exactly that many speech tokens, EOS and fill ids never drawn — so that benchmark work is deterministic without a checkpoint.
         device_output (an extension, non-streaming coalesced calls only): 'tts_speech' stays on the model's device instead of the reference's
-        CPU tensor -- for a caller that hands the waveform to a device-side consumer (cv2amd/shard.py: the RCCL gather of configs[3])."""
+        CPU tensor -- for a caller that hands the waveform to a device-side consumer (cv2amd/shard.py: the RCCL gather of configs[3]).
+        output_sample_rate, pcm16 (an extension, every mode): 'tts_speech' at 8000 / 16000 / 22050 / 32000 / 44100 / 48000 Hz instead of
+        24000 and / or as int16 PCM, converted on the device before the copy to the host; a stream's chunks concatenate to the conversion
+        of the whole call.  A non-final chunk may then be empty.  The defaults take exactly the path without them."""
         from collections.abc import Generator
         vc = source_speech_token.shape[1] != 0                   # vc_job (model.py:141-143): the tokens are given, no LLM
         bistream = isinstance(text, Generator)                    # llm_job's bistream branch (model.py:120-128)
@@ -1151,6 +1237,9 @@ class CosyVoice2Model:
             raise TypeError('text must be a tensor of token ids or a generator of such tensors')
         if stream is True and speed != 1.0:
             S.check_speed(speed)               # streaming stretches within [0.5, 2] (cv2amd/stretch.py): refused before any work
+        if output_sample_rate is not None:
+            O.check_rate(output_sample_rate)   # one of cv2amd.outrate.RATES: refused before any work
+        out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
         this_uuid = str(uuid.uuid1())
         # the current device is per thread and a new thread starts on device 0: callers run tts() from pool threads (the evaluation
         # harness, evaluation/cosyvoice_synthesizer.py:260) while the model may live on another GPU of the node (one rank per GPU)
@@ -1166,6 +1255,8 @@ class CosyVoice2Model:
             self.hift_cache_dict[this_uuid] = None
             if stream is True and speed != 1.0:
                 self.stretch_dict[this_uuid] = self._Stretcher(speed)
+            if pcm16 or out_rate != O.MODEL_RATE:
+                self.out_dict[this_uuid] = self._Out(out_rate, pcm16, self.device)
         if bistream and not vc:
             with self._bi_cv:                                                 # the hub waits (briefly) for calls on their way in before its first feed
                 self._bi_incoming += 1
@@ -1187,7 +1278,7 @@ class CosyVoice2Model:
             p = self._Pending()
             p.text, p.prompt_text, p.llm_ptok = text.to(dev), prompt_text.to(dev), llm_prompt_speech_token.to(dev)
             p.fpt, p.feat, p.femb, p.speed, p.uuid, p.force_len = fpt, feat, femb, speed, this_uuid, force_len
-            p.dev_out = bool(device_output)
+            p.dev_out, p.out = bool(device_output), self.out_dict.get(this_uuid)
             p.done, p.speech, p.exc = threading.Event(), None, None
             try:
                 yield {'tts_speech': self._tts_coalesced(p)}
@@ -1197,6 +1288,7 @@ class CosyVoice2Model:
                     self.llm_end_dict.pop(this_uuid, None)
                     self.hift_cache_dict.pop(this_uuid, None)
                     self.stretch_dict.pop(this_uuid, None)
+                    self.out_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
             return
@@ -1262,7 +1354,7 @@ class CosyVoice2Model:
                         break
                 with self.run_lock:
                     this_tok = torch.tensor(toks, dtype=torch.int32).unsqueeze(0)
-                    speech = self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed).cpu()
+                    speech = self._out_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed)).cpu()
                 yield {'tts_speech': speech}
         finally:
             with self.run_lock, self.llm_lock:                                # an abandoned generator leaves a live slot behind: park it
@@ -1280,5 +1372,6 @@ class CosyVoice2Model:
                 self.llm_end_dict.pop(this_uuid, None)
                 self.hift_cache_dict.pop(this_uuid, None)
                 self.stretch_dict.pop(this_uuid, None)
+                self.out_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)

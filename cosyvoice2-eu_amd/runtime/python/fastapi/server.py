@@ -1,6 +1,8 @@
 """HTTP server of the reference (runtime/python/fastapi/server.py:40-81) over the MI355X CosyVoice2: every endpoint streams the yielded
-chunks as int16 PCM.  Form / file uploads need python-multipart (as in the reference); `build_app` raises a clear error without it."""
+chunks as int16 PCM, at the server's --sample_rate or the request's optional `sample_rate` form field (resampled and converted on the
+device when the model was built with output_pcm16).  Form / file uploads need python-multipart (as in the reference); `build_app` raises a clear error without it."""
 import argparse
+from typing import Optional
 import os
 import sys
 
@@ -12,7 +14,7 @@ import wire  # noqa: E402
 
 def generate_data(model_output):
     for i in model_output:
-        yield wire.pcm16(i['tts_speech'])
+        yield wire.pcm_bytes(i['tts_speech'])
 
 
 def build_app(cosyvoice):
@@ -23,26 +25,36 @@ def build_app(cosyvoice):
     app = FastAPI()
     app.add_middleware(CORSMiddleware, allow_origins=['*'], allow_credentials=True, allow_methods=['*'], allow_headers=['*'])
 
+    def at(sample_rate):
+        """the model at the request's rate (None: the server's); an unsupported rate is the client's error"""
+        if sample_rate is None:
+            return cosyvoice
+        try:
+            return cosyvoice.output(sample_rate=sample_rate)
+        except ValueError as e:
+            from fastapi import HTTPException
+            raise HTTPException(status_code=422, detail=str(e))
+
     @app.get('/inference_zero_shot')
     @app.post('/inference_zero_shot')
-    async def inference_zero_shot(tts_text: str = Form(), prompt_text: str = Form(), prompt_wav: UploadFile = File()):
-        return StreamingResponse(generate_data(cosyvoice.inference_zero_shot(tts_text, prompt_text, load_wav(prompt_wav.file, 16000))))
+    async def inference_zero_shot(tts_text: str = Form(), prompt_text: str = Form(), prompt_wav: UploadFile = File(), sample_rate: Optional[int] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate).inference_zero_shot(tts_text, prompt_text, load_wav(prompt_wav.file, 16000))))
 
     @app.get('/inference_cross_lingual')
     @app.post('/inference_cross_lingual')
-    async def inference_cross_lingual(tts_text: str = Form(), prompt_wav: UploadFile = File()):
-        return StreamingResponse(generate_data(cosyvoice.inference_cross_lingual(tts_text, load_wav(prompt_wav.file, 16000))))
+    async def inference_cross_lingual(tts_text: str = Form(), prompt_wav: UploadFile = File(), sample_rate: Optional[int] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate).inference_cross_lingual(tts_text, load_wav(prompt_wav.file, 16000))))
 
     @app.get('/inference_instruct2')
     @app.post('/inference_instruct2')
-    async def inference_instruct2(tts_text: str = Form(), instruct_text: str = Form(), prompt_wav: UploadFile = File()):
-        return StreamingResponse(generate_data(cosyvoice.inference_instruct2(tts_text, instruct_text, load_wav(prompt_wav.file, 16000))))
+    async def inference_instruct2(tts_text: str = Form(), instruct_text: str = Form(), prompt_wav: UploadFile = File(), sample_rate: Optional[int] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate).inference_instruct2(tts_text, instruct_text, load_wav(prompt_wav.file, 16000))))
 
     @app.get('/inference_sft')
     @app.post('/inference_sft')
-    async def inference_sft(tts_text: str = Form(), spk_id: str = Form()):
+    async def inference_sft(tts_text: str = Form(), spk_id: str = Form(), sample_rate: Optional[int] = Form(None)):
         # CosyVoice2 has no SFT speakers of its own; a registered zero-shot speaker id plays that role (cli/cosyvoice.py:70-76)
-        return StreamingResponse(generate_data(cosyvoice.inference_zero_shot(tts_text, '', None, zero_shot_spk_id=spk_id)))
+        return StreamingResponse(generate_data(at(sample_rate).inference_zero_shot(tts_text, '', None, zero_shot_spk_id=spk_id)))
     return app
 
 
@@ -50,7 +62,8 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--port', type=int, default=50000)
     ap.add_argument('--model_dir', type=str, required=True)
+    ap.add_argument('--sample_rate', type=int, default=None, help='rate of the PCM sent (8000, 16000, 22050, 24000, 32000, 44100, 48000); default: the model\'s 24000')
     args = ap.parse_args()
     import uvicorn
     from cosyvoice.cli.cosyvoice import CosyVoice2
-    uvicorn.run(build_app(CosyVoice2(args.model_dir, final=True)), host='0.0.0.0', port=args.port)
+    uvicorn.run(build_app(CosyVoice2(args.model_dir, final=True, output_sample_rate=args.sample_rate, output_pcm16=True)), host='0.0.0.0', port=args.port)

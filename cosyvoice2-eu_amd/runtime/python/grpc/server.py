@@ -1,5 +1,5 @@
 """gRPC server of the reference (runtime/python/grpc/server.py:33-76) over the MI355X CosyVoice2: rpc Inference(Request) -> stream of
-Response{tts_audio = int16 PCM}.  No generated stubs: the messages are (de)serialised by runtime/python/wire.py."""
+Response{tts_audio = int16 PCM} (at --sample_rate; resampled and converted on the device, the proto is untouched).  No generated stubs: the messages are (de)serialised by runtime/python/wire.py."""
 import argparse
 import logging
 import os
@@ -28,7 +28,7 @@ class CosyVoiceServiceImpl:
         else:
             out = self.cosyvoice.inference_instruct(f['tts_text'], f['spk_id'], f['instruct_text'])
         for i in out:
-            yield wire.pcm16(i['tts_speech'])
+            yield wire.pcm_bytes(i['tts_speech'])
 
 
 def make_server(cosyvoice, port, max_conc=4):
@@ -48,10 +48,11 @@ if __name__ == '__main__':
     ap.add_argument('--port', type=int, default=50000)
     ap.add_argument('--max_conc', type=int, default=4)
     ap.add_argument('--model_dir', type=str, required=True)
+    ap.add_argument('--sample_rate', type=int, default=None, help='rate of the PCM sent (8000, 16000, 22050, 24000, 32000, 44100, 48000); default: the model\'s 24000')
     args = ap.parse_args()
     logging.basicConfig(level=logging.DEBUG, format='%(asctime)s %(levelname)s %(message)s')
     from cosyvoice.cli.cosyvoice import CosyVoice2
-    srv, _ = make_server(CosyVoice2(args.model_dir, final=True), args.port, args.max_conc)
+    srv, _ = make_server(CosyVoice2(args.model_dir, final=True, output_sample_rate=args.sample_rate, output_pcm16=True), args.port, args.max_conc)
     srv.start()
     logging.info('server listening on 0.0.0.0:{}'.format(args.port))
     srv.wait_for_termination()

@@ -22,6 +22,13 @@ def pcm16(wave):
     return (a * (2 ** 15)).astype(np.int16).tobytes()
 
 
+def pcm_bytes(wave):
+    """what a server sends for a yielded chunk: an int16 tensor / array (the model produced PCM16 on the device: output_pcm16) goes
+    out as its own bytes, a float one through pcm16."""
+    a = wave.numpy() if hasattr(wave, 'numpy') else np.asarray(wave)
+    return np.ascontiguousarray(a).astype('<i2', copy=False).tobytes() if a.dtype == np.int16 else pcm16(a)
+
+
 def pcm16_to_float(buf):
     """grpc/server.py:49-50: int16 bytes -> float32 [1, n] / 2**15."""
     return (np.frombuffer(buf, dtype=np.int16).astype(np.float32) / (2 ** 15))[None, :]

@@ -419,6 +419,38 @@ int cv2_mel_stretch(const cv2_stretch_args* a, int32_t rows, void* stream);     
  * memory, uploaded by the caller ahead of this call on `stream` -- the kernel reads its stream's record from there. */
 int cv2_mel_stretch_batch(const cv2_stretch_args* args, const cv2_stretch_args* table_dev, int32_t n, int32_t rows, void* stream);
 
+/* Output rate and sample format of a call (an extension: the reference hands back float32 at 24 kHz and nothing else): the waveform resampled
+ * to a target rate R and / or converted to int16 PCM on the device, ahead of the device-to-host copy, chunk-invariant when streaming.
+ * s[0 .. N) are the 24 kHz samples a call yields, in order (a streaming call: the concatenation of its chunks after cross-fade and cache
+ * trim).  g = gcd(24000, R), down = 24000 / g, up = R / g; K[up][klen] and width are torchaudio's sinc_interp_hann table for 24000 -> R
+ * (lowpass width 6, rolloff 0.99, fp64 rounded once to fp32: cv2amd.prompt._sinc_kernel, the table cv2_resample takes).  Output sample
+ * o = i up + p, 0 <= p < up, is
+ *     y[o] = sum over j = 0 .. klen - 1 with 0 <= q < N of K[p][j] s[q],   q = i down - width + j,
+ * ONE fp32 fmaf chain in ascending j from 0.f; taps outside [0, N) are skipped, not multiplied by zero (k_resample's order: a stream equals
+ * cv2_resample of the whole signal bit for bit, whatever the chunking).  The call emits ceil(N up / down) samples in all.  Before the final
+ * chunk o goes out as soon as i down - width + klen - 1 <= n_available - 1; the final chunk emits the rest.  Retained per call: the source
+ * samples from max(0, i_next down - width) on (fewer than klen + down).  All index arithmetic is integer; cv2amd/outrate.py plans it.
+ * One record = one call's chunk: the source samples first .. n_available - 1 as two pieces, `tail` (n_tail samples from global index `first`
+ * on) and `fresh` (the n_available - first - n_tail new ones), both fp32 device; the outputs o0 .. o0 + n_emit - 1 go to dst[0 .. n_emit),
+ * float (CV2_OUT_F32) or int16 (CV2_OUT_PCM16: trunc_toward_zero(y * 32768) saturated to [-32768, 32767], NaN -> 0; for in-range values
+ * the servers' (x * 2**15).astype(int16)).  dst is aligned to its element only; dst_cap = elements it can take.  n_final: -1 while more
+ * samples will come, else = n_available.  kernel = NULL with up = down = klen = 1, width = 0: no filter (R = 24000), the samples pass through
+ * exactly.  Records of one batch may differ in rate and format.  Adding these entry points changed no struct and no signature:
+ * CV2_ABI_VERSION stays. */
+#define CV2_OUT_F32 0
+#define CV2_OUT_PCM16 1
+typedef struct {
+    const float* tail; const float* fresh; void* dst; const float* kernel;
+    int32_t first, n_tail, n_avail, n_final;
+    int32_t o0, n_emit;
+    int32_t up, down, klen, width;
+    int32_t format, dst_cap;
+} cv2_out_args;                                                      /* 80 bytes */
+int cv2_out_resample(const cv2_out_args* a, void* stream);                        /* a: host */
+/* n calls as ONE launch (gridDim.z = n): `args` are the n records on the host (checked here), `table_dev` the same n records in device
+ * memory, uploaded by the caller ahead of this call on `stream`. */
+int cv2_out_resample_batch(const cv2_out_args* args, const cv2_out_args* table_dev, int32_t n, void* stream);
+
 /* =====================================================================================================================
  * Prompt features (the extractor that feeds this path): replaces the reference's
  *   feat_extractor = matcha.utils.audio.mel_spectrogram(n_fft 1920, num_mels 80, sampling_rate 24000, hop_size 480, win_size 1920,

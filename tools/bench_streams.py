@@ -1,8 +1,9 @@
 """First-chunk latency of N concurrent streaming calls on ONE model (BASELINE config 5: streaming, B = 8):
-python tools/bench_streams.py [streams] [rounds] [--stagger MS] [--speed S] [--fresh-threads] [--trace].  Each round starts N calls at once (or within MS
+python tools/bench_streams.py [streams] [rounds] [--stagger MS] [--speed S] [--pcm16 RATE] [--fresh-threads] [--trace].  Each round starts N calls at once (or within MS
 milliseconds of each other); reports p50 / max of the time from a call to its first chunk and the p50 gap between a stream's chunks.
 --speed S: every call streams at that speed (the mel time-stretch of DESIGN section 1); the line then also says how the non-final chunks
-reached the vocoder: through inference_batch (chunks of one shape in one set of launches) or singly."""
+reached the vocoder: through inference_batch (chunks of one shape in one set of launches) or singly.
+--pcm16 RATE: every call asks for int16 PCM at RATE Hz (output_sample_rate / pcm16, DESIGN section 1: one more launch per chunk round)."""
 import os, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'cosyvoice2-eu_amd'))
@@ -10,7 +11,7 @@ import torch
 from cv2amd import synth
 from cosyvoice.cli.model import CosyVoice2Model
 
-_a = [x for i, x in enumerate(sys.argv[1:]) if not x.startswith('--') and sys.argv[i] not in ('--stagger', '--speed')]
+_a = [x for i, x in enumerate(sys.argv[1:]) if not x.startswith('--') and sys.argv[i] not in ('--stagger', '--speed', '--pcm16')]
 N = int(_a[0]) if len(_a) > 0 else 8
 R = int(_a[1]) if len(_a) > 1 else 4
 m = CosyVoice2Model(synth.make_llm(), synth.make_flow(), synth.make_hift(), max_text=128, max_prompt_tokens=320, max_new_tokens=1100,
@@ -24,6 +25,8 @@ kw = dict(text=inp['text'], prompt_text=inp['prompt_text'], llm_prompt_speech_to
 
 import random
 SPEED = float(sys.argv[sys.argv.index('--speed') + 1]) if '--speed' in sys.argv else 1.0
+OUT_RATE = int(sys.argv[sys.argv.index('--pcm16') + 1]) if '--pcm16' in sys.argv else None
+OUT_KW = dict(output_sample_rate=OUT_RATE, pcm16=True) if OUT_RATE else {}
 _how = {'batched': 0, 'single': 0}               # non-final chunks of shared rounds: vocoder calls through inference_batch / one by one
 if m.hift_pool.batch_engine is not None:
     _ib, _one = m.hift_pool.batch_engine.inference_batch, m.hift.inference
@@ -79,14 +82,14 @@ def run(n):
             time.sleep(_rng.random() * STAGGER * 1e-3)
             t_call = time.perf_counter()
         t_prev = None
-        for out in m.tts(**kw, stream=True, speed=SPEED):
+        for out in m.tts(**kw, stream=True, speed=SPEED, **OUT_KW):
             now = time.perf_counter()
             if first[i] is None:
                 first[i] = now - t_call
             else:
                 gaps.append(now - t_prev)
             t_prev = now
-            total[i] += out['tts_speech'].shape[1] / 24000.0
+            total[i] += out['tts_speech'].shape[1] / float(OUT_RATE or 24000)
     if POOL:
         _pool.run(work, n)
     else:
@@ -117,6 +120,6 @@ for n in (1, N):
         firsts += f
         gaps += g
     firsts.sort(); gaps.sort()
-    print(f'speed {SPEED}: {n} concurrent stream(s): first chunk p50 {firsts[len(firsts) // 2] * 1e3:.1f} ms, max {firsts[-1] * 1e3:.1f} ms; '
+    print(f'speed {SPEED}{f", int16 PCM at {OUT_RATE} Hz" if OUT_RATE else ""}: {n} concurrent stream(s): first chunk p50 {firsts[len(firsts) // 2] * 1e3:.1f} ms, max {firsts[-1] * 1e3:.1f} ms; '
           f'chunk gap p50 {gaps[len(gaps) // 2] * 1e3 if gaps else 0.0:.1f} ms; last round {audio:.1f} s of audio in {dt:.2f} s = {audio / dt:.1f} audio-s/s; '
           f'non-final chunks in shared rounds: {_how["batched"]} through inference_batch, {_how["single"]} singly', flush=True)
