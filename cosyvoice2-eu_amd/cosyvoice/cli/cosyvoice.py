@@ -27,6 +27,7 @@ class CosyVoice2:
             from cv2amd import outrate
             outrate.check_rate(output_sample_rate)                          # refused before anything is loaded
         self.output_sample_rate, self.output_pcm16 = output_sample_rate, bool(output_pcm16)
+        self.sampling = None                                                # a .sampler(...) view's Sampling; None: the model's sampler and counter seed
         self.model_dir = model_dir
         self.fp16 = fp16
         self.model_sample_rate = 24000                                      # conf/cosyvoice2.yaml:8; what the frontends receive as resample_rate
@@ -112,6 +113,22 @@ class CosyVoice2:
         view.output_pcm16 = self.output_pcm16 if pcm16 is None else bool(pcm16)
         return view
 
+    def sampler(self, seed=None, temperature=None, top_p=None, top_k=None, win_size=None, tau_r=None, greedy=None):
+        """A view of this object (same model, same frontend) whose calls carry their own sampler settings and / or seed: what a server
+        uses for a request that wants a reproducible, a more conservative or a livelier reading.  None keeps this object's setting (the
+        model's where it has none).  seed 0 .. 2**64 - 1, temperature 0.05 .. 10, top_p (0, 1], top_k 1 .. 25, win_size 1 .. 64,
+        tau_r >= 0, greedy True / False; anything else raises ValueError here, before the model is touched.  A seeded call draws the
+        same uniforms and the same vocoder noise whatever else the model is serving; the segments of a split text
+        use streams 0, 1, 2, ... of the one seed.  Composes with .output()."""
+        import copy
+        from cv2amd.sampling import Sampling
+        new = Sampling(seed=seed, temperature=temperature, top_p=top_p, top_k=top_k, win_size=win_size, tau_r=tau_r, greedy=greedy).check()
+        view = copy.copy(self)
+        if self.sampling is not None:
+            new = self.sampling.replace(**{k: getattr(new, k) for k in ('seed', 'temperature', 'top_p', 'top_k', 'win_size', 'tau_r', 'greedy')})
+        view.sampling = None if new.is_default() else new
+        return view
+
     def list_available_spks(self):
         return list(self.frontend.spk2info.keys())
 
@@ -126,12 +143,14 @@ class CosyVoice2:
     def save_spkinfo(self):
         torch.save(self.frontend.spk2info, '{}/spk2info.pt'.format(self.model_dir))
 
-    def _run(self, model_input, stream, speed, label):
+    def _run(self, model_input, stream, speed, label, segment=0):
         start_time = time.time()
         logging.info('synthesis text {}'.format(label))
         extra = {}
         if self.output_sample_rate is not None or self.output_pcm16:
             extra = dict(output_sample_rate=self.output_sample_rate, pcm16=self.output_pcm16)
+        if self.sampling is not None:                                       # (segment k of a split text: stream k under the one seed)
+            extra['sampling'] = self.sampling.for_segment(segment)
         for model_output in self.model.tts(**model_input, stream=stream, speed=speed, **extra):
             speech_len = model_output['tts_speech'].shape[1] / self.sample_rate
             logging.info('yield speech len {}, rtf {}'.format(speech_len, (time.time() - start_time) / speech_len))
@@ -141,22 +160,22 @@ class CosyVoice2:
     def inference_sft(self, tts_text, spk_id, stream=False, speed=1.0, text_frontend=True):
         """cli/cosyvoice.py:81-90 (inherited by CosyVoice2): a speaker of spk2info by id, no prompt.  A CosyVoice2 model dir has no
         spk2info.pt, so an unknown `spk_id` raises the reference's KeyError (frontend.py:487)."""
-        for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
+        for seg, i in enumerate(self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend)):
             model_input = self.frontend.frontend_sft(i, spk_id)
-            yield from self._run(model_input, stream, speed, i)
+            yield from self._run(model_input, stream, speed, i, seg)
 
     def inference_zero_shot(self, tts_text, prompt_text, prompt_speech_16k, zero_shot_spk_id='', stream=False, speed=1.0, text_frontend=True):
         prompt_text = self.frontend.text_normalize(prompt_text, split=False, text_frontend=text_frontend)
-        for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
+        for seg, i in enumerate(self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend)):
             if isinstance(i, str) and len(i) < 0.5 * len(prompt_text):
                 logging.warning('synthesis text {} too short than prompt text {}, this may lead to bad performance'.format(i, prompt_text))
             model_input = self.frontend.frontend_zero_shot(i, prompt_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
-            yield from self._run(model_input, stream, speed, i)
+            yield from self._run(model_input, stream, speed, i, seg)
 
     def inference_cross_lingual(self, tts_text, prompt_speech_16k, zero_shot_spk_id='', stream=False, speed=1.0, text_frontend=True):
-        for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
+        for seg, i in enumerate(self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend)):
             model_input = self.frontend.frontend_cross_lingual(i, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
-            yield from self._run(model_input, stream, speed, i)
+            yield from self._run(model_input, stream, speed, i, seg)
 
     def inference_vc(self, source_speech_16k, prompt_speech_16k, stream=False, speed=1.0):
         """cli/cosyvoice.py:132-139: voice conversion = the source utterance's speech tokens through flow + HiFT with the prompt's voice."""
@@ -168,6 +187,6 @@ class CosyVoice2:
 
     def inference_instruct2(self, tts_text, instruct_text, prompt_speech_16k, zero_shot_spk_id='', stream=False, speed=1.0, text_frontend=True):
         """cli/cosyvoice.py:284-295: same three stages, the instruction rides in the prompt-text slot."""
-        for i in self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend):
+        for seg, i in enumerate(self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend)):
             model_input = self.frontend.frontend_instruct2(i, instruct_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
-            yield from self._run(model_input, stream, speed, i)
+            yield from self._run(model_input, stream, speed, i, seg)

@@ -40,6 +40,7 @@ from cv2amd.llm import LLMEngine, MODE_RAS, MODE_GREEDY
 from cv2amd import lib as L
 from cv2amd import stretch as S
 from cv2amd import outrate as O
+from cv2amd import sampling as SP
 
 
 class _FairLock:
@@ -151,6 +152,7 @@ class CosyVoice2Model:
         self.hift_cache_dict = {}
         self.stretch_dict = {}                 # uuid -> _Stretcher of a streaming call with speed != 1; created and dropped with hift_cache_dict[uuid]
         self.out_dict = {}                     # uuid -> _Out of a call with output_sample_rate / pcm16; created and dropped with hift_cache_dict[uuid]
+        self.samp_dict = {}                    # uuid -> [Sampling, vocoder invocations so far] of a call with its own sampler settings / seed; likewise
         self._hift_pin, self._pin_rr = {}, -1  # uuid -> index of the HiftPool engine / HIP stream serving that call's chunks
         self.llm_stream = torch.cuda.Stream(self.device)   # (torch.cuda.Stream.priority_range() is (0, -1) here: no priority below the default exists)
         self.sampling_mode = MODE_RAS if sampling == 'ras' else MODE_GREEDY
@@ -232,6 +234,15 @@ class CosyVoice2Model:
                                          finalize=finalize)
         return self._mel2wav(tts_mel, token_offset, uuid, finalize, speed)
 
+    def _vocoder_seed(self, uuid):
+        """The noise seed of the call's next vocoder invocation: hift_seed(seed, segment, 0, 1, 2, ...) for a call that carries a seed
+        (a function of the call alone), None = the pool's counter."""
+        rec = self.samp_dict.get(uuid)
+        if rec is None or rec[0].seed is None:
+            return None
+        rec[1] += 1
+        return SP.hift_seed(rec[0].seed, rec[0].stream, rec[1] - 1)
+
     def _chunk_post(self, uuid, cache, tts_mel, tts_speech, tts_source, hift):
         """model.py:316-324 after the vocoder of a non-final chunk: cross-fade with the cached speech tail, new caches, trim."""
         if cache is not None:
@@ -288,10 +299,12 @@ class CosyVoice2Model:
             for j0 in range(0, len(idx), eng.lanes):
                 part = idx[j0:j0 + eng.lanes]
                 try:
+                    vs = [self._vocoder_seed(grp[i].uuid) for i in part]
                     if len(part) >= 2 and T <= eng.max_frames:
-                        res = eng.inference_batch([pre[i][1] for i in part], [pre[i][2] for i in part])
+                        seeds = None if all(v is None for v in vs) else [self.hift_pool.next_seed() if v is None else v for v in vs]
+                        res = eng.inference_batch([pre[i][1] for i in part], [pre[i][2] for i in part], seeds=seeds)
                     else:
-                        res = [self.hift.inference(speech_feat=pre[i][1], cache_source=pre[i][2]) for i in part]
+                        res = [self.hift.inference(speech_feat=pre[i][1], cache_source=pre[i][2], seed=v) for i, v in zip(part, vs)]
                     for i, (wav, src) in zip(part, res):
                         out[i] = self._chunk_post(grp[i].uuid, pre[i][0], pre[i][1], wav, src, self.hift)
                 except Exception as e:
@@ -428,14 +441,15 @@ class CosyVoice2Model:
             noise = self._noise_hook(n_frames, uuid) if self._noise_hook_takes_uuid else self._noise_hook(n_frames)
         if self._trace is not None:
             self._trace.append((flow_mel.cpu(), token_offset, finalize, noise, uuid))
+        vseed = self._vocoder_seed(uuid)
         if finalize is False:
-            tts_speech, tts_source = hift.inference(speech_feat=tts_mel.contiguous(), cache_source=hift_cache_source, noise=noise)
+            tts_speech, tts_source = hift.inference(speech_feat=tts_mel.contiguous(), cache_source=hift_cache_source, noise=noise, seed=vseed)
             tts_speech = self._chunk_post(uuid, cache, tts_mel, tts_speech, tts_source, hift)
         else:
             if speed != 1.0 and sx is None:
                 assert cache is None, 'speed change only support non-stream inference mode'
                 tts_mel = hift.change_speed(tts_mel, speed)                     # F.interpolate(mode='linear') of model.py:329, on the device
-            tts_speech, tts_source = hift.inference(speech_feat=tts_mel.contiguous(), cache_source=hift_cache_source, noise=noise)
+            tts_speech, tts_source = hift.inference(speech_feat=tts_mel.contiguous(), cache_source=hift_cache_source, noise=noise, seed=vseed)
             if cache is not None:
                 hift.fade_in_out(tts_speech, cache['speech'], self._window_dev)
         return tts_speech
@@ -714,15 +728,16 @@ class CosyVoice2Model:
             self._mode.notify_all()
 
     class _Prefill:
-        __slots__ = ('slot', 'text', 'prompt_text', 'ptok', 'done', 'exc', 'force_len')
+        __slots__ = ('slot', 'text', 'prompt_text', 'ptok', 'done', 'exc', 'force_len', 'sampling')
 
-    def _llm_start(self, slot, text, prompt_text, llm_prompt_speech_token, force_len=None):
+    def _llm_start(self, slot, text, prompt_text, llm_prompt_speech_token, force_len=None, sampling=None):
         """llm.py:684-719 step 0 (prefill + first draw) for one call.  Calls that start together are prefilled TOGETHER: the request
         is queued, whoever gets the device next runs one batched prefill (one pass over the weights) for every queued request."""
         if self._sched_log is not None:
             self._sched_log.append((time.perf_counter(), 'start', dict(slot=slot)))
         p = self._Prefill()
         p.slot, p.text, p.prompt_text, p.ptok, p.done, p.exc, p.force_len = slot, text, prompt_text, llm_prompt_speech_token, False, None, force_len
+        p.sampling = sampling
         with self.lock:
             self._prefill_q.append(p)
         if self.newcomer_beside:
@@ -760,11 +775,12 @@ class CosyVoice2Model:
                             if not grp:
                                 continue
                             gx, gm = [xs[batch.index(b)] for b in grp], [mms[batch.index(b)] for b in grp]
+                            gs = [b.sampling for b in grp]                     # (seeded, unseeded, RAS and greedy calls may share the prefill)
                             if sum(x.shape[0] for x in gx) <= self.llm.dims.max_prefill_rows:
-                                self.llm.add_requests([b.slot for b in grp], gx, gm, self.sampling_mode, self.seed, forced)
+                                self.llm.add_requests([b.slot for b in grp], gx, gm, self.sampling_mode, self.seed, forced, gs)
                             else:
                                 for b, x, mm in zip(grp, gx, gm):
-                                    self.llm.add_requests([b.slot], [x], [mm], self.sampling_mode, self.seed, forced)
+                                    self.llm.add_requests([b.slot], [x], [mm], self.sampling_mode, self.seed, forced, [b.sampling])
                         ev = torch.cuda.Event()
                         ev.record(self.llm_stream)
                     for b in batch:
@@ -870,7 +886,7 @@ class CosyVoice2Model:
 
     # ---- coalesced non-streaming calls ---------------------------------------------------------------------------
     class _Pending:
-        __slots__ = ('text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'speed', 'uuid', 'done', 'speech', 'exc', 'force_len', 'dev_out', 'out')
+        __slots__ = ('text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'speed', 'uuid', 'done', 'speech', 'exc', 'force_len', 'dev_out', 'out', 'sampling')
 
     def _run_batch(self, batch):
         """llm_job + token2wav(finalize=True) of model.py:118-139,300-334 for several queued calls at once.  Only the caller whose
@@ -884,7 +900,7 @@ class CosyVoice2Model:
                 fl = None
             toks, errs = self.llm.generate([(p.text, p.prompt_text, p.llm_ptok) for p in batch], mode=self.sampling_mode, seed=self.seed,
                                            return_errors=True, min_ratio=self.min_token_text_ratio, max_ratio=self.max_token_text_ratio,
-                                           force_len=fl)
+                                           force_len=fl, sampling=[p.sampling for p in batch])
             with self.lock:
                 for p, t in zip(batch, toks):
                     self.tts_speech_token_dict[p.uuid], self.llm_end_dict[p.uuid] = t, True
@@ -910,7 +926,8 @@ class CosyVoice2Model:
                 if p.speed != 1.0:                                            # model.py:328-330
                     m = self.hift.change_speed(m, p.speed)
                 gm.append(m.contiguous())
-            outs = self.hift_pool.inference_many(gm) if gm else []
+            vs = [self._vocoder_seed(p.uuid) for p, _ in good]
+            outs = self.hift_pool.inference_many(gm, seeds=None if all(v is None for v in vs) else vs) if gm else []
             torch.cuda.synchronize(self.device)
             conv = {}
             cj = [(k, (p.out, wav, True)) for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)) if p.out is not None]
@@ -1145,7 +1162,7 @@ class CosyVoice2Model:
                     self.llm_end_dict[c.uuid] = True
             self._bi_cv.notify_all()
 
-    def _tts_pulled(self, text, prompt_text, llm_ptok, source_speech_token, fpt, feat, femb, this_uuid, stream, speed, vc):
+    def _tts_pulled(self, text, prompt_text, llm_ptok, source_speech_token, fpt, feat, femb, this_uuid, stream, speed, vc, sampling=None):
         """tts() for the two token sources that are not the batched unistream LLM: voice conversion (vc_job, model.py:141-143: the
         speech tokens of the source utterance ARE the tokens) and generator text (inference_bistream, llm.py:721-834: the call owns
         one LLM slot, the hub above drives it together with every other generator-text call).  The chunk arithmetic is model.py:351-394."""
@@ -1161,7 +1178,8 @@ class CosyVoice2Model:
                 self.llm_end_dict[this_uuid] = True
             else:
                 self.seed += 1
-                call = self._bi_register(self.llm.new_bistream(slot, prompt_text, llm_ptok, mode=self.sampling_mode, seed=self.seed), this_uuid, text)
+                call = self._bi_register(self.llm.new_bistream(slot, prompt_text, llm_ptok, mode=self.sampling_mode, seed=self.seed, sampling=sampling),
+                                          this_uuid, text)
                 incoming = False
 
             def pull(n_total):
@@ -1213,6 +1231,7 @@ class CosyVoice2Model:
                 self.hift_cache_dict.pop(this_uuid, None)
                 self.stretch_dict.pop(this_uuid, None)
                 self.out_dict.pop(this_uuid, None)
+                self.samp_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
 
@@ -1222,14 +1241,17 @@ class CosyVoice2Model:
             llm_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             flow_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             prompt_speech_feat=torch.zeros(1, 0, 80), source_speech_token=torch.zeros(1, 0, dtype=torch.int32), stream=False, speed=1.0,
-            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, **kwargs):
+            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, sampling=None, **kwargs):
         """force_len (an extension; the reference swallows unknown keywords in **kwargs): synthetic-weights mode of SURVEY.md §8(d) —
         exactly that many speech tokens, EOS and fill ids never drawn — so that benchmark work is deterministic without a checkpoint.
         device_output (an extension, non-streaming coalesced calls only): 'tts_speech' stays on the model's device instead of the reference's
         CPU tensor -- for a caller that hands the waveform to a device-side consumer (cv2amd/shard.py: the RCCL gather of configs[3]).
         output_sample_rate, pcm16 (an extension, every mode): 'tts_speech' at 8000 / 16000 / 22050 / 32000 / 44100 / 48000 Hz instead of
         24000 and / or as int16 PCM, converted on the device before the copy to the host; a stream's chunks concatenate to the conversion
-        of the whole call.  A non-final chunk may then be empty.  The defaults take exactly the path without them."""
+        of the whole call.  A non-final chunk may then be empty.  The defaults take exactly the path without them.
+        sampling (an extension, every mode): a cv2amd.sampling.Sampling -- the call's own sampler settings (temperature, top_p, top_k, win_size,
+        tau_r, greedy) and seed.  A seeded call's LLM draws and vocoder noise are functions of (seed, segment, step, trial) / (seed, segment,
+        chunk) alone, whatever slot, batch or round serves it.  None, or nothing set: the model's sampler and counter seed."""
         from collections.abc import Generator
         vc = source_speech_token.shape[1] != 0                   # vc_job (model.py:141-143): the tokens are given, no LLM
         bistream = isinstance(text, Generator)                    # llm_job's bistream branch (model.py:120-128)
@@ -1239,6 +1261,8 @@ class CosyVoice2Model:
             S.check_speed(speed)               # streaming stretches within [0.5, 2] (cv2amd/stretch.py): refused before any work
         if output_sample_rate is not None:
             O.check_rate(output_sample_rate)   # one of cv2amd.outrate.RATES: refused before any work
+        if sampling is not None:
+            sampling = None if sampling.is_default() else sampling.check()      # out-of-range settings: refused before any work
         out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
         this_uuid = str(uuid.uuid1())
         # the current device is per thread and a new thread starts on device 0: callers run tts() from pool threads (the evaluation
@@ -1257,6 +1281,8 @@ class CosyVoice2Model:
                 self.stretch_dict[this_uuid] = self._Stretcher(speed)
             if pcm16 or out_rate != O.MODEL_RATE:
                 self.out_dict[this_uuid] = self._Out(out_rate, pcm16, self.device)
+            if sampling is not None:
+                self.samp_dict[this_uuid] = [sampling, 0]
         if bistream and not vc:
             with self._bi_cv:                                                 # the hub waits (briefly) for calls on their way in before its first feed
                 self._bi_incoming += 1
@@ -1272,23 +1298,26 @@ class CosyVoice2Model:
             raise
         if vc or bistream:
             yield from self._tts_pulled(text, prompt_text, llm_prompt_speech_token, source_speech_token, fpt, feat, femb, this_uuid,
-                                        stream, speed, vc)
+                                        stream, speed, vc, sampling)
             return
         if stream is not True and self.max_batch > 1 and self._noise_hook is None and self._trace is None:
             p = self._Pending()
             p.text, p.prompt_text, p.llm_ptok = text.to(dev), prompt_text.to(dev), llm_prompt_speech_token.to(dev)
             p.fpt, p.feat, p.femb, p.speed, p.uuid, p.force_len = fpt, feat, femb, speed, this_uuid, force_len
-            p.dev_out, p.out = bool(device_output), self.out_dict.get(this_uuid)
+            p.dev_out, p.out, p.sampling = bool(device_output), self.out_dict.get(this_uuid), sampling
             p.done, p.speech, p.exc = threading.Event(), None, None
             try:
                 yield {'tts_speech': self._tts_coalesced(p)}
             finally:
                 with self.lock:
+                    if self._token_log is not None:
+                        self._token_log[this_uuid] = list(self.tts_speech_token_dict.get(this_uuid, []))
                     self.tts_speech_token_dict.pop(this_uuid, None)
                     self.llm_end_dict.pop(this_uuid, None)
                     self.hift_cache_dict.pop(this_uuid, None)
                     self.stretch_dict.pop(this_uuid, None)
                     self.out_dict.pop(this_uuid, None)
+                    self.samp_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
             return
@@ -1312,7 +1341,7 @@ class CosyVoice2Model:
                 with self.lock:
                     self._first_pending[this_uuid] = t_call
                     self._first_need[slot] = hop + prompt_token_pad + la        # (model.py:353-357: what the first chunk waits for)
-                self._llm_start(slot, text_d, ptext_d, lptok_d, force_len)     # prefill draws token 0; the first pass of the loop below
+                self._llm_start(slot, text_d, ptext_d, lptok_d, force_len, sampling)     # prefill draws token 0; the first pass of the loop below
                 while True:                                                    # requests the rest of the first chunk's tokens
                     this_tok, finished = None, False
                     with self.run_lock:
@@ -1339,7 +1368,7 @@ class CosyVoice2Model:
                 speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True, speed=speed)
                 yield {'tts_speech': speech}
             else:
-                self._llm_start(slot, text_d, ptext_d, lptok_d, force_len)
+                self._llm_start(slot, text_d, ptext_d, lptok_d, force_len, sampling)
                 n_min = force_len if force_len is not None else int(text.shape[1] * self.min_token_text_ratio)
                 n_max = force_len if force_len is not None else int(text.shape[1] * self.max_token_text_ratio)
                 done_steps = 1                                                 # the prefill drew step 0
@@ -1373,5 +1402,6 @@ class CosyVoice2Model:
                 self.hift_cache_dict.pop(this_uuid, None)
                 self.stretch_dict.pop(this_uuid, None)
                 self.out_dict.pop(this_uuid, None)
+                self.samp_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)

@@ -22,6 +22,11 @@ class Cosy2EU:
     def sample_rate(self) -> int:
         return getattr(self._model, 'sample_rate', 24000)
 
+    def sampler(self, seed=None, temperature=None, top_p=None, top_k=None, win_size=None, tau_r=None, greedy=None) -> 'Cosy2EU':
+        """A view of this object (same model) whose calls carry their own sampler settings / seed: CosyVoice2.sampler."""
+        return Cosy2EU(self._model.sampler(seed=seed, temperature=temperature, top_p=top_p, top_k=top_k, win_size=win_size, tau_r=tau_r,
+                                           greedy=greedy))
+
     def tts(self, text: str, prompt: str, *, speed: float = 1.0, text_frontend: bool = False) -> Tuple[torch.Tensor, int]:
         prompt_16k = load_wav(prompt, 16000)
         segments = [out['tts_speech'] for out in self._model.inference_cross_lingual(text, prompt_16k, stream=False, speed=speed,

@@ -22,6 +22,7 @@ extern __device__ unsigned long long g_chain_t[1024][8];
 #include "gemm_launch.h"
 #include "../../include/cv2_amd.h"
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <stdlib.h>
 #include <stdarg.h>
@@ -1386,6 +1387,7 @@ struct SampleArgs {
     int prefill_seq, row, prefill_pos;          // prefill: one block, reads logits row `row`, updates slot prefill_seq,
     unsigned* epoch;                            // hand-off epoch of k_chain: advanced once per launch (chain.h)
     const int* slots; float* x_rows;            // decode over live slots: block b serves slot slots[b] and also leaves the next input in row b
+    const cv2_llm_sampling* samp;               // [max_seqs] per-slot sampling records (cv2_llm_set_sampling), used where state[slot][CV2_ST_SAMP] != 0
 };                                              // whose next KV position becomes prefill_pos (= prompt length)
 #define SM_T 1024
 #define SM_W (SM_T / 64)
@@ -1491,12 +1493,31 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
 #pragma unroll
         for (int i = 0; i < ST; i++) sv[i] = stc[i];
     }
-    // the first trial's uniforms depend on the state record only (counter = (slot, step, 0), key = seed): one lane of wave 1 draws them
+    // the slot's sampling record: requested unconditionally beside the state record (one more block-uniform 32-byte read at an address
+    // that depends on the slot only, so a request with its own settings adds no dependent round trip); CV2_ST_SAMP selects between it
+    // and the engine's constants.  All of these are block-uniform scalars.  The clamps keep a record written behind
+    // cv2_llm_set_sampling's back inside the candidate arrays and the window's wave.
+    const cv2_llm_sampling* __restrict__ rp = a.samp + seq;
+    float r_it = rp->inv_temp, r_tp = rp->top_p, r_rt = rp->rep_thr;
+    int r_tk = rp->top_k, r_win = rp->win_size;
+    uint32_t r_ctr = rp->stream;
+    // (the empty statement consumes the six words in scalar registers: without it the compiler sinks the record's loads behind the
+    // branch on CV2_ST_SAMP, i.e. behind the state record's arrival)
+    // (... and the state record's last two words, so that it stays two 8-word loads issued with the record's instead of a late single word)
+    asm volatile("" : "+s"(r_it), "+s"(r_tp), "+s"(r_tk), "+s"(r_win), "+s"(r_rt), "+s"(r_ctr) : "s"(sv[CV2_ST_WAIT]), "s"(sv[CV2_ST_SAMP]));
+    const bool own = sv[CV2_ST_SAMP] != 0;
+    const float inv_temp = own ? r_it : 1.0f;
+    const float top_p = own ? r_tp : a.top_p;
+    const int top_k = own ? min(max(r_tk, 1), SM_TOPK) : a.top_k;
+    const int win = own ? min(max(r_win, 0), 64) : a.win;
+    const float rep_thr = own ? r_rt : a.rep_thr;
+    const uint32_t ctr0 = own ? r_ctr : (uint32_t)seq;                  // Philox counter word 0: the request's stream, else the slot
+    // the first trial's uniforms depend on the two records only (counter = (slot or stream, step, 0), key = seed): one lane of wave 1 draws them
     // while the logits are still on their way -- the ten Philox rounds were ~500 cycles of the sampling lane's serial draw phase
     __shared__ double s_u0[2];
     if (tid == 64) {
         uint32_t rn[4];
-        philox4x32((uint32_t)seq, (uint32_t)sv[CV2_ST_STEP], 0u, 0u, (uint32_t)sv[CV2_ST_SEED_LO], (uint32_t)sv[CV2_ST_SEED_HI], rn);
+        philox4x32(ctr0, (uint32_t)sv[CV2_ST_STEP], 0u, 0u, (uint32_t)sv[CV2_ST_SEED_LO], (uint32_t)sv[CV2_ST_SEED_HI], rn);
         s_u0[0] = u53(rn[0], rn[1]); s_u0[1] = u53(rn[2], rn[3]);
     }
     // CV2_ST_ERR == 3: a hand-off of this step's k_step timed out (chain.h) -- the logits are not this step's: nothing is drawn and
@@ -1504,11 +1525,11 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
     // flag and run the step again on the launches
     const int done = sv[CV2_ST_DONE] | (sv[CV2_ST_ERR] == 3 ? 1 : 0);
     const int step = sv[CV2_ST_STEP];
-    // repetition window (last 10 emitted tokens): lanes 0..9 of wave 0 hold one entry each; a serial loop of dependent global
+    // repetition window (last win <= 64 emitted tokens, 10 at the defaults): lanes 0..win-1 of wave 0 hold one entry each; a serial loop of dependent global
     // loads in the sampling thread cost ~10 memory round trips per step
     const int nhist = min(sv[CV2_ST_NOUT], a.max_out);                      // (nout never passes max_out: the slot finishes there)
     int hv = -1;
-    if (tid < a.win && nhist - a.win + tid >= 0) hv = a.out_tokens[(size_t)seq * a.max_out + nhist - a.win + tid];
+    if (tid < win && nhist - win + tid >= 0) hv = a.out_tokens[(size_t)seq * a.max_out + nhist - win + tid];
     // bistream (inference_bistream, llm.py:721-834): bimode 1 = text still expected (EOS always re-drawn, the fill id eos + 2 stops
     // the slot until the host has fed the next text block and is FORCED every n_speech + 1 entries once it has appeared), 2 = final
     // decode (EOS ends the request); out_tokens then holds every drawn id incl. fill / EOS, as the reference's list does
@@ -1537,8 +1558,12 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
             best = block_argmax(best, sam);
             if (tid == 0) s_top = best.i;
         } else {
-            // RAS (utils/common.py:111-139): top-p 0.8 / top-k 25 nucleus, repetition window 10, tau 0.1
+            // RAS (utils/common.py:111-139): top-p 0.8 / top-k 25 nucleus, repetition window 10, tau 0.1 (or the slot's record)
             const int lane = tid & 63, w = tid >> 6;
+            // temperature: z = logits * inv_temp, one fp32 multiply rounded on its own (never contracted into the z - max below); 1.0f is
+            // the identity, and the masks above stay -inf
+#pragma unroll
+            for (int e = 0; e < SM_NE; e++) lv[e] = __fmul_rn(lv[e], inv_temp);
             unsigned tk = 0u;                                                 // this thread's largest key (0 = none: every real key is > 0)
 #pragma unroll
             for (int e = 0; e < SM_NE; e++) if (tid + e * SM_T < V) { const unsigned k = fkey(lv[e]); tk = k > tk ? k : tk; }
@@ -1575,7 +1600,7 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
                 int r = 0;
 #pragma unroll
                 for (int j = 0; j < SM_T / 16; j++) { const unsigned o = rowmax[j]; r += (o > mine || (o == mine && j < lane)) ? 1 : 0; }
-                if (r == a.top_k - 1) s_thr = mine;
+                if (r == top_k - 1) s_thr = mine;
             }
             __syncthreads();
             const unsigned thr = s_thr;
@@ -1603,7 +1628,8 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
 #pragma unroll
                         for (int u = 0; u < 8; u++) r += (j0 + u < ncnd && (o[u] > mk || (o[u] == mk && oi[u] < mi))) ? 1 : 0;
                     }
-                    if (r < a.top_k) { candi[r] = mi; candp[r] = __expf(fkey_inv(mk)); }
+                    // ranks top_k .. 24 (a record's smaller nucleus) hold probability 0: all 25 entries are defined for the sums below
+                    if (r < SM_TOPK) { candi[r] = mi; candp[r] = r < top_k ? __expf(fkey_inv(mk)) : 0.f; }
                 }
                 if (tid >= ncnd && tid < SM_TOPK) { candi[tid] = 0; candp[tid] = 0.f; }   // vocabulary smaller than the nucleus
                 // the candidate lists are written by threads < max(ncnd, 25) and read by thread 0 alone (here and in the draw below): with
@@ -1622,9 +1648,10 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
                     int nc = 0; float before = 0.f;
 #pragma unroll
                     for (int c = 0; c < SM_TOPK; c++) {
-                        nc += (c < a.top_k && before < a.top_p) ? 1 : 0;
+                        nc += (c < top_k && before < top_p) ? 1 : 0;
                         before += cp[c];
                     }
+                    nc = nc > 0 ? nc : 1;                                      // (top_p > 0 makes it >= 1; a record written behind the entry point's back must not index candi[-1])
                     ncand_r = nc;
                     s_ncand = nc;
                 }
@@ -1677,7 +1704,8 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
                     }
                     if (lane == 0) {
                         int nc = 0; float cum = 0.f;
-                        while (nc < a.top_k && cum < a.top_p) { cum += candp[nc]; nc++; }
+                        while (nc < top_k && cum < top_p) { cum += candp[nc]; nc++; }
+                        nc = nc > 0 ? nc : 1;
                         ncand_r = nc;
                         s_ncand = nc;
                     }
@@ -1697,7 +1725,7 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
                         if (trial == 0) { u1 = s_u0[0]; s_u2 = s_u0[1]; }      // (drawn at kernel entry; the barriers since then order the LDS write)
                         else {
                             uint32_t rn[4];
-                            philox4x32((uint32_t)seq, (uint32_t)step, (uint32_t)trial, 0u, (uint32_t)sv[CV2_ST_SEED_LO], (uint32_t)sv[CV2_ST_SEED_HI], rn);
+                            philox4x32(ctr0, (uint32_t)step, (uint32_t)trial, 0u, (uint32_t)sv[CV2_ST_SEED_LO], (uint32_t)sv[CV2_ST_SEED_HI], rn);
                             u1 = u53(rn[0], rn[1]);
                             s_u2 = u53(rn[2], rn[3]);
                         }
@@ -1728,7 +1756,7 @@ __global__ __launch_bounds__(SM_T) void k_sample(SampleArgs a) {
                     const int rep = __popcll(__ballot(hv == top));             // hv = -1 where the window has no entry
                     if (tid == 0) {
                         s_top = top;
-                        s_need = (float)rep >= a.rep_thr;                      // rep_num >= win_size * tau_r -> random_sampling over the full vocabulary
+                        s_need = (float)rep >= rep_thr;                      // rep_num >= win_size * tau_r -> random_sampling over the full vocabulary
                         s_done = 0;
                         if (!s_need) {
                             if (!ignore_eos || top != a.eos) s_done = 1;
@@ -2128,6 +2156,7 @@ struct cv2_llm {
     StepLayer* step_layers;    // device copy of the per-layer pointer table
     int step_blocks;
     unsigned* epoch;           // hand-off epoch (device), advanced by k_sample
+    cv2_llm_sampling* samp;    // [max_seqs] per-slot sampling records (cv2_llm_set_sampling; read by k_sample where CV2_ST_SAMP != 0)
     size_t chain_off, chain_bytes;   // the region cv2_llm_create zeroes
     bool use_chain;            // a one-row decode step is ONE launch, k_step (CV2_LLM_CHAIN=0: the five launches per layer)
     std::map<int, hipGraphExec_t> graphs;
@@ -2192,6 +2221,7 @@ static size_t carve(const cv2_llm_dims& d, cv2_llm* h, char* base) {
         p = take((2 * R + 6 * 32) * 4); if (h) h->pf_int = (int*)p;
         p = take((size_t)PF_SPLITK * PF_SPLIT_ROWS * d.hidden * 4); if (h) h->pf_parts = (float*)p;
     }
+    p = take((size_t)d.max_seqs * sizeof(cv2_llm_sampling)); if (h) h->samp = (cv2_llm_sampling*)p;
     return off;
 }
 
@@ -2239,6 +2269,10 @@ extern "C" int cv2_llm_create(const cv2_llm_dims* d, const cv2_llm_weights* w, c
                        d->n_q * 64 / 4 <= 240 && (d->hidden / 16) % 4 == 0 && rep * 64 + rep * 2 <= AT_GSTRIDE && rep * 64 <= 512 && ntiles * d->n_kv <= 64 &&
                        d->hidden % 2 == 0;
         const unsigned one = 1u;
+        // every slot's sampling record starts as the engine's constants with stream = the slot: what CV2_ST_SAMP = 0 selects anyway
+        std::vector<cv2_llm_sampling> recs(d->max_seqs);
+        for (int i = 0; i < d->max_seqs; i++)
+            recs[i] = cv2_llm_sampling{1.0f, h->d.top_p, h->d.top_k, h->d.win_size, (float)h->d.win_size * h->d.tau_r, (uint32_t)i, {0, 0}};
         std::vector<StepLayer> tab(d->layers);
         const size_t cache_l = (size_t)d->max_seqs * d->n_kv * d->max_pos * 64;
         for (int l = 0; l < d->layers; l++) {
@@ -2247,7 +2281,8 @@ extern "C" int cv2_llm_create(const cv2_llm_dims* d, const cv2_llm_weights* w, c
         }
         if (hipMemset((char*)ws + h->chain_off, 0, h->chain_bytes) != hipSuccess ||
             hipMemcpy(h->epoch, &one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->step_layers, tab.data(), tab.size() * sizeof(StepLayer), hipMemcpyHostToDevice) != hipSuccess) {
+            hipMemcpy(h->step_layers, tab.data(), tab.size() * sizeof(StepLayer), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(h->samp, recs.data(), recs.size() * sizeof(cv2_llm_sampling), hipMemcpyHostToDevice) != hipSuccess) {
             if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
             delete h;
             return cv2_fail("cv2_llm_create: initialising the hand-off state failed");
@@ -2505,8 +2540,27 @@ static int launch_sample(cv2_llm* h, int nblocks, int prefill_seq, int row, int 
     const cv2_llm_dims& d = h->d;
     SampleArgs a{h->io.logits, d.vocab_pad, h->io.state, h->io.out_tokens, d.max_out, h->w.speech_emb, h->xnext,
                  d.hidden, d.vocab, d.eos, d.max_pos, 15, d.top_p, d.top_k, d.win_size, (float)d.win_size * d.tau_r, prefill_seq, row, prefill_pos,
-                 h->epoch, mapped ? h->row_slots : nullptr, mapped ? h->xrows : nullptr};
+                 h->epoch, mapped ? h->row_slots : nullptr, mapped ? h->xrows : nullptr, h->samp};
     hipLaunchKernelGGL(k_sample, dim3(nblocks), dim3(SM_T), 0, s, a);
+    CV2_LAUNCH_CHECK();
+    return 0;
+}
+
+// One slot's sampling record, written in stream order (ahead of the state row and the prefill the caller enqueues next): the record
+// travels by value in the launch arguments and one lane stores it.
+__global__ void k_set_sampling(cv2_llm_sampling* dst, cv2_llm_sampling rec) {
+    if (threadIdx.x == 0) *dst = rec;
+}
+
+extern "C" int cv2_llm_set_sampling(cv2_llm* h, int32_t slot, const cv2_llm_sampling* r, void* stream) {
+    CV2_CHECK(h && r, "cv2_llm_set_sampling: null argument");
+    CV2_CHECK(slot >= 0 && slot < h->d.max_seqs, "cv2_llm_set_sampling: bad slot %d", slot);
+    CV2_CHECK(std::isfinite(r->inv_temp) && r->inv_temp > 0.f, "cv2_llm_set_sampling: inv_temp must be finite and > 0");
+    CV2_CHECK(r->top_p > 0.f && r->top_p <= 1.f, "cv2_llm_set_sampling: top_p %g outside (0, 1]", (double)r->top_p);
+    CV2_CHECK(r->top_k >= 1 && r->top_k <= SM_TOPK, "cv2_llm_set_sampling: top_k %d outside 1..%d", r->top_k, SM_TOPK);
+    CV2_CHECK(r->win_size >= 1 && r->win_size <= 64, "cv2_llm_set_sampling: win_size %d outside 1..64", r->win_size);
+    CV2_CHECK(std::isfinite(r->rep_thr) && r->rep_thr >= 0.f, "cv2_llm_set_sampling: rep_thr must be finite and >= 0");
+    hipLaunchKernelGGL(k_set_sampling, dim3(1), dim3(64), 0, (hipStream_t)stream, h->samp + slot, *r);
     CV2_LAUNCH_CHECK();
     return 0;
 }

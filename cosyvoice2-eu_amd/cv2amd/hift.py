@@ -329,8 +329,9 @@ class HiftPool:
             self._seed += 1
             return self._salt ^ self._seed
 
-    def inference_many(self, mels):
-        """mels: list of [1,80,T] device tensors.  Returns list of (wav, source)."""
+    def inference_many(self, mels, seeds=None):
+        """mels: list of [1,80,T] device tensors.  Returns list of (wav, source).  seeds: None, or one noise seed per mel (None entries
+        and seeds=None draw from the pool's counter)."""
         main = torch.cuda.current_stream()
         outs = [None] * len(mels)
         for st in self.streams:
@@ -338,7 +339,8 @@ class HiftPool:
         for i, mel in enumerate(mels):
             k = i % len(self.engines)
             with torch.cuda.stream(self.streams[k]):
-                outs[i] = self.engines[k].inference(mel, None, seed=self.next_seed())
+                own = seeds[i] if seeds is not None else None
+                outs[i] = self.engines[k].inference(mel, None, seed=self.next_seed() if own is None else own)
             for t in outs[i]:
                 t.record_stream(main)
         for st in self.streams:

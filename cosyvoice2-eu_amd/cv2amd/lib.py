@@ -12,7 +12,7 @@ _lib = None
 
 STATE_STRIDE = 16
 (ST_POS, ST_STEP, ST_NOUT, ST_DONE, ST_MINLEN, ST_MAXLEN, ST_MODE, ST_FORCE, ST_SEED_LO, ST_SEED_HI, ST_ERR, ST_LAST, ST_BIMODE, ST_NEXTFILL,
- ST_WAIT) = range(15)
+ ST_WAIT, ST_SAMP) = range(16)
 
 
 class Cv2Error(RuntimeError):
@@ -36,6 +36,12 @@ class LlmWeights(C.Structure):
 
 class LlmIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('state', 'out_tokens', 'logits')]
+
+
+class LlmSampling(C.Structure):
+    """cv2_llm_sampling: one slot's sampler settings and Philox stream (cv2amd/sampling.py builds the values)"""
+    _fields_ = [('inv_temp', C.c_float), ('top_p', C.c_float), ('top_k', C.c_int32), ('win_size', C.c_int32), ('rep_thr', C.c_float),
+                ('stream', C.c_uint32), ('reserved', C.c_int32 * 2)]
 
 
 def lib():
@@ -62,6 +68,7 @@ def lib():
         L.cv2_llm_debug_ptrs.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.cv2_llm_debug_skip_publish.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.cv2_llm_debug_sample.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.cv2_llm_set_sampling.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LlmSampling), C.c_void_p]
         L.cv2_flow_debug_attn_dma.argtypes = [C.c_int32]
         L.cv2_flow_debug_graph.argtypes = [C.c_int32]
         L.cv2_hift_debug_modes.argtypes = [C.c_int32, C.c_int32]
@@ -95,7 +102,7 @@ def ptr(t):
 
 
 EXPORTS = ['cv2_last_error', 'cv2_version', 'cv2_llm_workspace_bytes', 'cv2_llm_create', 'cv2_llm_destroy',
-           'cv2_llm_prefill', 'cv2_llm_prefill_batch', 'cv2_llm_extend', 'cv2_llm_extend_batch', 'cv2_llm_decode', 'cv2_llm_decode_ex', 'cv2_llm_decode_rows', 'cv2_llm_one_launch_step', 'cv2_llm_debug_ptrs', 'cv2_llm_debug_skip_publish', 'cv2_llm_debug_sample', 'cv2_skinny_gemm', 'cv2_gemm_bf16', 'cv2_gemm_f16',
+           'cv2_llm_prefill', 'cv2_llm_prefill_batch', 'cv2_llm_extend', 'cv2_llm_extend_batch', 'cv2_llm_decode', 'cv2_llm_decode_ex', 'cv2_llm_decode_rows', 'cv2_llm_one_launch_step', 'cv2_llm_debug_ptrs', 'cv2_llm_debug_skip_publish', 'cv2_llm_debug_sample', 'cv2_llm_set_sampling', 'cv2_skinny_gemm', 'cv2_gemm_bf16', 'cv2_gemm_f16',
            'cv2_flow_workspace_bytes', 'cv2_flow_create', 'cv2_flow_destroy', 'cv2_flow_inference', 'cv2_flow_inference_chunk', 'cv2_flow_cache_bytes', 'cv2_flow_cache_copy', 'cv2_flow_debug_attn_dma', 'cv2_flow_debug_graph', 'cv2_flow_estimator',
            'cv2_flow_encoder', 'cv2_hift_workspace_bytes', 'cv2_hift_create', 'cv2_hift_destroy', 'cv2_hift_inference', 'cv2_hift_inference_batch', 'cv2_hift_debug_modes', 'cv2_hift_debug_precision', 'cv2_hift_debug_f0',
            'cv2_fade_in_out', 'cv2_interp_linear', 'cv2_mel_stretch', 'cv2_mel_stretch_batch', 'cv2_out_resample', 'cv2_out_resample_batch', 'cv2_melspec', 'cv2_resample', 'cv2_framefeat', 'cv2_whisper_post', 'cv2_sub_col_mean', 'cv2_dbg_act', 'cv2_dbg_pre']

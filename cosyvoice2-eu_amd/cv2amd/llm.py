@@ -36,6 +36,8 @@ class LLMEngine:
                               max_prefill_rows=(max_prefill_rows if max_prefill_rows is not None else min(max_seqs * 512, max_seqs * max_pos)),
                               **{k: (sampling or {}).get(k, v) for k, v in (('top_p', 0.8), ('top_k', 25), ('win_size', 10), ('tau_r', 0.1))})
         self.hidden, self.max_seqs, self.max_out, self.vocab, self.vocab_pad = hidden, max_seqs, max_out, vocab, vocab_pad
+        # the engine's ras_sampling constants: what a per-request Sampling (cv2amd/sampling.py) leaves unset
+        self.sampling_defaults = dict(top_p=self.dims.top_p, top_k=self.dims.top_k, win_size=self.dims.win_size, tau_r=self.dims.tau_r)
         keep = []
 
         def dv(t, dtype=torch.float32):
@@ -107,13 +109,45 @@ class LLMEngine:
         ps = prompt_speech_token.reshape(-1).to(dev).long()
         return torch.cat([self.llm_emb[0:1], self.text_emb[ids], self.llm_emb[1:2], self.speech_emb[ps]], dim=0).contiguous()
 
-    def add_request(self, slot, lm_input, min_len, max_len, mode=MODE_GREEDY, seed=0, force_len=False):
-        """Step 0 of inference_wrapper (llm.py:684-719): prefill + first draw for `slot`."""
-        self._init_state(slot, min_len, max_len, mode, seed, force_len)
+    def add_request(self, slot, lm_input, min_len, max_len, mode=MODE_GREEDY, seed=0, force_len=False, sampling=None):
+        """Step 0 of inference_wrapper (llm.py:684-719): prefill + first draw for `slot`.  sampling: the request's own sampler settings
+        and seed (cv2amd.sampling.Sampling), None = the engine's constants with Philox draws keyed by the slot."""
+        self._init_state(slot, min_len, max_len, *self._apply_sampling(slot, sampling, mode, seed), force_len)
         assert lm_input.dtype == torch.float32 and lm_input.is_contiguous() and lm_input.shape[1] == self.hidden
         L.check(self.lib.cv2_llm_prefill(self.handle, slot, L.ptr(lm_input), lm_input.shape[0], L.stream_ptr()))
 
-    def _init_state(self, slot, min_len, max_len, mode, seed, force_len):
+    def set_sampling(self, slot, rec):
+        """the slot's cv2_llm_sampling record (a dict of its fields, Sampling.record()), written in stream order; raises for values out of range"""
+        r = L.LlmSampling(inv_temp=rec['inv_temp'], top_p=rec['top_p'], top_k=rec['top_k'], win_size=rec['win_size'], rep_thr=rec['rep_thr'],
+                          stream=rec['stream'])
+        L.check(self.lib.cv2_llm_set_sampling(self.handle, slot, C.byref(r), L.stream_ptr()))
+
+    def _apply_sampling(self, slot, sampling, mode, seed):
+        """(mode, seed, CV2_ST_SAMP) of a request: a Sampling with anything set writes the slot's record (ahead of the state row and the
+        prefill, on the same stream) and may replace the mode (greedy) and the seed; nothing set = the caller's mode and seed, no record."""
+        if sampling is None or sampling.is_default():
+            return mode, seed, 0
+        sampling.check()
+        self.set_sampling(slot, self._record(slot, sampling))
+        if sampling.greedy is not None:
+            mode = MODE_GREEDY if sampling.greedy else (mode if mode != MODE_GREEDY else MODE_RAS)
+        return mode, (seed if sampling.seed is None else sampling.seed), 1
+
+    def _record(self, slot, sampling):
+        """the slot's record of a request with settings: Philox counter word 0 is the segment index under the request's OWN seed; a
+        request without one runs under its caller's seed, which the requests started beside it share, and keeps the slot there, as
+        without a record -- settings alone never make two requests draw the same uniforms"""
+        return sampling.record(self.sampling_defaults, stream=None if sampling.seed is not None else slot)
+
+    @staticmethod
+    def _per(v, n):
+        """one value for all n requests, or a list of n"""
+        if isinstance(v, (list, tuple)):
+            assert len(v) == n
+            return list(v)
+        return [v] * n
+
+    def _init_state(self, slot, min_len, max_len, mode, seed, samp, force_len):
         # every step emits at most one token into out_tokens[slot, :max_out]: a request may not run longer than the buffer
         # (the reference has no such buffer: `for i in range(max_len)`, llm.py:684; max_out is sized for 20 x the text limit)
         if max_len > self.max_out:
@@ -125,13 +159,16 @@ class LLMEngine:
         st[L.ST_MINLEN], st[L.ST_MAXLEN], st[L.ST_MODE], st[L.ST_FORCE] = min_len, max_len, mode, int(force_len)
         st[L.ST_SEED_LO] = (seed & 0x7FFFFFFF) - (seed & 0x80000000)
         st[L.ST_SEED_HI] = ((seed >> 32) & 0x7FFFFFFF) - ((seed >> 32) & 0x80000000)
+        st[L.ST_SAMP] = samp
         self.state[slot].copy_(st)
 
-    def add_requests(self, slots, lm_inputs, lens_minmax, mode=MODE_GREEDY, seed=0, force_len=False):
-        """Step 0 for several slots in one pass over the weights (cv2_llm_prefill_batch): lm_inputs = list of [L0, hidden] fp32."""
+    def add_requests(self, slots, lm_inputs, lens_minmax, mode=MODE_GREEDY, seed=0, force_len=False, sampling=None):
+        """Step 0 for several slots in one pass over the weights (cv2_llm_prefill_batch): lm_inputs = list of [L0, hidden] fp32.
+        sampling: None or a list aligned with the slots (entries None or Sampling); mode and seed may be lists too."""
         n = len(slots)
-        for slot, (mn, mx) in zip(slots, lens_minmax):
-            self._init_state(slot, mn, mx, mode, seed, force_len)
+        modes, seeds, samps = self._per(mode, n), self._per(seed, n), self._per(sampling, n)
+        for slot, (mn, mx), m, sd_, sp in zip(slots, lens_minmax, modes, seeds, samps):
+            self._init_state(slot, mn, mx, *self._apply_sampling(slot, sp, m, sd_), force_len)
         emb = torch.cat([x.reshape(-1, self.hidden) for x in lm_inputs], 0).to(torch.float32).contiguous()
         sl = (C.c_int32 * n)(*slots)
         ln = (C.c_int32 * n)(*[x.shape[0] for x in lm_inputs])
@@ -222,12 +259,14 @@ class LLMEngine:
             self.state[slot, L.ST_DONE] = 1
 
     def generate(self, requests, mode=MODE_GREEDY, seed=0, force_len=None, sync_every=16, min_ratio=2, max_ratio=20, batch_prefill=True,
-                 return_errors=False, compact=True):
+                 return_errors=False, compact=True, sampling=None):
         """requests: list of (text, prompt_text, prompt_speech_token) int tensors.  Returns list of token lists; with
         return_errors=True also a list holding None or the RuntimeError of each request (a failing request finishes its own slot and
-        never stops the others), otherwise the first error is raised."""
+        never stops the others), otherwise the first error is raised.  sampling: None or a list aligned with the requests (= slots 0 .. n-1);
+        mode and seed may be lists as well."""
         n = len(requests)
         assert n <= self.max_seqs
+        modes, seeds, samps = self._per(mode, n), self._per(seed, n), self._per(sampling, n)
         xs, mm = [], []
         forced = force_len is not None
         fl = list(force_len) if isinstance(force_len, (list, tuple)) else [force_len] * n     # one forced length for all, or one per request
@@ -238,10 +277,10 @@ class LLMEngine:
             xs.append(self.build_lm_input(text, ptxt, ptok))
             mm.append((mn, mx))
         if batch_prefill and sum(x.shape[0] for x in xs) <= self.dims.max_prefill_rows:
-            self.add_requests(list(range(n)), xs, mm, mode, seed, forced)
+            self.add_requests(list(range(n)), xs, mm, modes, seeds, forced, samps)
         else:
             for b in range(n):
-                self.add_request(b, xs[b], mm[b][0], mm[b][1], mode, seed, forced)
+                self.add_request(b, xs[b], mm[b][0], mm[b][1], modes[b], seeds[b], forced, samps[b])
         while True:
             st = self.state[:n].cpu()                 # a poll reads the state records only (2 KB); the tokens are fetched once, at the end
             S = st.tolist()
@@ -271,9 +310,10 @@ class LLMEngine:
                 self.step(n, k)
 
     # ---- llm.py:721-834 ------------------------------------------------------------------------------------------
-    def new_bistream(self, slot, prompt_text, prompt_speech_token, mode=MODE_GREEDY, seed=0, mix_ratio=(5, 15)):
-        """Host bookkeeping of one Qwen2LM.inference_bistream call on slot `slot` (no device work)."""
-        return BiStream(self, slot, prompt_text, prompt_speech_token, mode, seed, mix_ratio)
+    def new_bistream(self, slot, prompt_text, prompt_speech_token, mode=MODE_GREEDY, seed=0, mix_ratio=(5, 15), sampling=None):
+        """Host bookkeeping of one Qwen2LM.inference_bistream call on slot `slot` (no device work: a Sampling is checked here, its record
+        is written by the call's first bi_feed)."""
+        return BiStream(self, slot, prompt_text, prompt_speech_token, mode, seed, mix_ratio, sampling)
 
     def bi_poll(self, streams):
         """Read the slots of the RUNNING streams (one copy of the state records, one of the new out_tokens entries): new ids, fill /
@@ -307,6 +347,9 @@ class LLMEngine:
         if not feeds:
             return []
         dev = self.device
+        for b, _ in feeds:                                 # a call's own sampler record goes in ahead of its first state row
+            if not b.started and b.sampling is not None:
+                self.set_sampling(b.slot, self._record(b.slot, b.sampling))
         rows = torch.tensor([b._state_row(final) for b, (_, final) in feeds], dtype=torch.int32)
         self.state.index_copy_(0, torch.tensor([b.slot for b, _ in feeds], dtype=torch.long).to(dev), rows.to(dev))
         emb = self.emb_all[torch.tensor([i for _, (idx, _) in feeds for i in idx], dtype=torch.long).to(dev)]
@@ -365,7 +408,7 @@ class LLMEngine:
         return max(1, min(c + [burst]))
 
     def bistream(self, slot, text, prompt_text, prompt_speech_token, mode=MODE_GREEDY, seed=0, mix_ratio=(5, 15), burst=16,
-                 n_seqs=None, on_device=None):
+                 n_seqs=None, on_device=None, sampling=None):
         """Qwen2LM.inference_bistream on slot `slot`: `text` is an iterable of int tensors [1, n] arriving over time; yields speech
         token ids as the reference generator does.  The LM input interleaves mix_ratio[0] text tokens with mix_ratio[1] speech
         tokens; the device stops the slot on the fill id (k_sample, CV2_ST_WAIT) and the next text block is fed exactly where the
@@ -373,7 +416,7 @@ class LLMEngine:
         scheduler's rounds over several calls, cosyvoice/cli/model.py); `on_device(fn)` runs fn() under the caller's device lock /
         stream; the next piece of `text` is only pulled when the slot has nothing left to feed, as the reference's `for` does."""
         run = on_device or (lambda fn: fn())
-        bs = self.new_bistream(slot, prompt_text, prompt_speech_token, mode, seed, mix_ratio)
+        bs = self.new_bistream(slot, prompt_text, prompt_speech_token, mode, seed, mix_ratio, sampling)
         it = iter(text)
         while not bs.finished:
             if bs.running:
@@ -394,13 +437,13 @@ class LLMEngine:
             except StopIteration:
                 bs.close()
 
-    def generate_fixed(self, requests, n_tokens, mode=MODE_RAS, seed=0):
+    def generate_fixed(self, requests, n_tokens, mode=MODE_RAS, seed=0, sampling=None):
         """Synthetic-weights mode: exactly n_tokens per request, EOS never drawn, no host sync inside the
         decode loop.  Returns (list of token lists, (start, end) torch events bracketing the n_tokens-1 decode steps)."""
         n = len(requests)
         assert n <= self.max_seqs and n_tokens <= self.max_out
         xs = [self.build_lm_input(text, ptxt, ptok) for (text, ptxt, ptok) in requests]
-        self.add_requests(list(range(n)), xs, [(n_tokens, n_tokens)] * n, mode, seed, True)
+        self.add_requests(list(range(n)), xs, [(n_tokens, n_tokens)] * n, mode, seed, True, sampling)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         self.step(n, n_tokens - 1)
@@ -416,8 +459,16 @@ class BiStream:
     half is the slot's state machine in k_sample.  No method touches the device: LLMEngine.bi_poll / bi_feed / bi_burst do, for one
     stream or for all the streams of a scheduler round at once."""
 
-    def __init__(self, eng, slot, prompt_text, prompt_speech_token, mode, seed, mix_ratio=(5, 15)):
+    def __init__(self, eng, slot, prompt_text, prompt_speech_token, mode, seed, mix_ratio=(5, 15), sampling=None):
         import collections
+        if sampling is not None and sampling.is_default():
+            sampling = None
+        if sampling is not None:                       # the call's own settings: mode and seed as LLMEngine._apply_sampling resolves them
+            sampling.check()
+            if sampling.greedy is not None:
+                mode = MODE_GREEDY if sampling.greedy else (mode if mode != MODE_GREEDY else MODE_RAS)
+            seed = seed if sampling.seed is None else sampling.seed
+        self.sampling = sampling
         self.eng, self.slot, self.mode, self.seed, self.mix = eng, slot, mode, seed, tuple(mix_ratio)
         self.text_cache = [int(t) for t in prompt_text.reshape(-1).tolist()]                       # llm.py:750-757
         self.sp_left = [eng.IDX_SPEECH + int(t) for t in prompt_speech_token.reshape(-1).tolist()]
@@ -486,6 +537,7 @@ class BiStream:
             row[L.ST_SEED_LO] = (seed & 0x7FFFFFFF) - (seed & 0x80000000)
             row[L.ST_SEED_HI] = ((seed >> 32) & 0x7FFFFFFF) - ((seed >> 32) & 0x80000000)
             row[L.ST_NEXTFILL] = -1
+            row[L.ST_SAMP] = 0 if self.sampling is None else 1
         else:
             row = list(self._row)
         row[L.ST_DONE], row[L.ST_WAIT], row[L.ST_BIMODE] = 0, 0, (2 if final else 1)

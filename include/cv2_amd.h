@@ -89,7 +89,7 @@ enum {
     CV2_ST_DONE = 3,     /* 1 once EOS was drawn or max_len reached */
     CV2_ST_MINLEN = 4,   /* int(text_len * min_token_text_ratio) */
     CV2_ST_MAXLEN = 5,   /* int(text_len * max_token_text_ratio) */
-    CV2_ST_MODE = 6,     /* 0 greedy (harness-defined), 1 RAS with the constants of cv2_llm_dims */
+    CV2_ST_MODE = 6,     /* 0 greedy (harness-defined), 1 RAS with the constants of cv2_llm_dims (or the slot's record, CV2_ST_SAMP) */
     CV2_ST_FORCE = 7,    /* 1: synthetic-weights mode, ids >= eos never drawn (fixed decode length) */
     CV2_ST_SEED_LO = 8,
     CV2_ST_SEED_HI = 9,
@@ -99,6 +99,8 @@ enum {
     CV2_ST_BIMODE = 12,  /* inference_bistream (llm.py:721-834): 0 unistream, 1 text still expected, 2 final decode */
     CV2_ST_NEXTFILL = 13,/* next_fill_index of llm.py:783 (-1: none yet); counts entries of out_tokens incl. fill ids */
     CV2_ST_WAIT = 14,    /* 1: the slot stopped on the fill id (eos + 2) and waits for cv2_llm_extend with the next text block */
+    CV2_ST_SAMP = 15,    /* 0: the sampler constants of cv2_llm_dims and Philox counter word 0 = the slot; 1: the slot's cv2_llm_sampling record
+                          * (cv2_llm_set_sampling) */
     CV2_LLM_STATE_STRIDE = 16
 };
 
@@ -163,6 +165,31 @@ int cv2_llm_debug_ptrs(cv2_llm* h, uint64_t* out);
  * tests/golden/sampler_ras.npz (decisions of the reference's functions under a committed table of uniforms = this sampler's Philox draws)
  * can be replayed on the device.  Updates the slots exactly as a decode step's draw does. */
 int cv2_llm_debug_sample(cv2_llm* h, int32_t n_rows, void* stream);
+
+/* Sampler settings of ONE request (an extension: the reference has one ras_sampling configuration per model and the process-wide torch RNG).
+ * The engine keeps one record per slot in its workspace (max_seqs records at an address fixed at create: captured decode steps stay valid);
+ * k_sample uses the record of a slot whose state row has CV2_ST_SAMP = 1 and the constants of cv2_llm_dims otherwise, row by row of one
+ * launch.  With a record, in a RAS mode (CV2_ST_MODE 1, test mode 5; greedy draws nothing and ignores it):
+ *   z[i] = logits[i] * inv_temp, ONE fp32 multiply rounded on its own (inv_temp = 1.0f: the identity), then the pipeline of CV2_ST_SAMP = 0 on z -- the
+ *   step-0 / forced-length / ignore_eos masks, log-softmax, the nucleus under top_p / top_k by the running fp32 sum, the repetition count over
+ *   the last win_size tokens against rep_thr, the full-vocabulary re-draw, up to 100 EOS re-draws (CV2_ST_ERR = 1);
+ *   every Philox draw has counter (stream, step, trial, 0) and key CV2_ST_SEED_LO / HI: the uniforms of a request are a function of
+ *   (seed, stream, step, trial) and not of the slot, the row or the other rows of the launch.  Requests that share one seed must differ in
+ *   `stream`: a caller that gives a request settings but no seed of its own writes stream = the slot, as with CV2_ST_SAMP = 0.
+ * Unistream, bistream and prefill draws alike.  At create every record holds the engine's constants with stream = its slot.
+ * cv2_llm_set_sampling checks the ranges (-1 and cv2_last_error otherwise) and writes the record in stream order (a one-block kernel that
+ * takes it by value): the caller writes it ahead of the state row and the prefill on the same stream.  Adding this entry point and state
+ * word changed no struct and no signature: CV2_ABI_VERSION stays. */
+typedef struct {
+    float    inv_temp;   /* float32(1 / temperature), formed on the host; finite, > 0 */
+    float    top_p;      /* (0, 1] */
+    int32_t  top_k;      /* 1 .. 25 */
+    int32_t  win_size;   /* 1 .. 64 */
+    float    rep_thr;    /* (float)win_size * tau_r, the fp32 product cv2_llm_create forms for the engine's constants; >= 0 */
+    uint32_t stream;     /* Philox counter word 0 in place of the slot */
+    int32_t  reserved[2];
+} cv2_llm_sampling;                                                  /* 32 bytes */
+int cv2_llm_set_sampling(cv2_llm* h, int32_t slot, const cv2_llm_sampling* s /* host */, void* stream);
 
 /* Stand-alone skinny GEMM used by the LLM (exported for unit tests and for the flow time-MLP):
  * out[r][n] = sum_k W[n][k] x[r][k] (+bias[n]); rows <= 32; W packed; K % 32 == 0; N % 16 == 0. */
