@@ -64,7 +64,7 @@ struct QkvArgs {
     float* kc; float* vc;                       // this layer's cache: [max_seqs][n_kv][max_pos][64]
     int max_pos;
     RowMap rm;
-    const float* sq; int nsq; float eps;        // PRE operand left un-normalised by k_store<.., LAST>: rstd[r] = rsqrt(sum_b sq[r][b] / K + eps), as k_gateup
+    const float* sq; int nsq; float eps;        // PRE operand left un-normalised by k_prep: rstd[r] = rsqrt(sum_b sq[r][b] / K + eps), as k_gateup
 };
 // block = (head, half): features {half*16 + i, half*16 + 32 + i : i < 16} so that the rotate-half partner is in-block
 template <int NB, bool PRE = false>
@@ -147,31 +147,7 @@ struct AttnArgs {
     int n_q, n_kv, max_pos, nsplit, keys_per_split;
     RowMap rm;
     int rep;                  // n_q / n_kv (<= 8), passed so that no block divides
-    // many-row launches (17..32 rows): the LAST split of a (row, kv head) to finish combines the splits and leaves the O projection's
-    // operand planes (what k_prep<true> did as a launch of its own).  arrive = [SK_ROWS_CAP][n_kv] counters, zero between launches
-    int* arrive; uint16_t* pre;
 };
-// Stores / loads that are coherent across the XCDs' L2s (sc1): what a last-arriving block reads of the other blocks' results
-__device__ __forceinline__ void st_agent(float* p, float v) {
-    __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_agent(const float* p) {
-    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-// Block-uniform: has every one of the `n` blocks that share `cnt` (this one included) left its results?  The callers' result stores are
-// st_agent; they are complete (vmcnt) before the barrier, the counter is bumped after it.  The last block re-arms the counter.
-__device__ __forceinline__ bool last_arriver(int* cnt, int n) {
-    __shared__ int s_last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == n - 1;
-        if (old == n - 1) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    return s_last != 0;
-}
 // element (row r, column c) of an operand in the layout the PRE kernels copy (skinny.h): [c / 32][r / 16][hi, lo][(c / 8) % 4][r % 16][c % 8]
 __device__ __forceinline__ void put_planes(uint16_t* pre, int r, int c, float v) {
     uint16_t* d = pre + ((size_t)((c >> 5) * 2 + (r >> 4)) * 2) * 512 + (((c >> 3) & 3) * 16 + (r & 15)) * 8 + (c & 7);
@@ -331,7 +307,7 @@ __global__ __launch_bounds__(256 * NSUB) void k_attn(AttnArgs a) {
             const float* pp = &po_s[u][e];
             o += sc * (((pp[0] + pp[512]) + (pp[1024] + pp[1536])) + ((pp[2048] + pp[2560]) + (pp[3072] + pp[3584])));
         }
-        if (a.arrive) st_agent(&po[e], o); else po[e] = o;
+        po[e] = o;
     }
     if (tid < rep) {
         float M = run_m[0][tid], l = 0.f;
@@ -339,41 +315,10 @@ __global__ __launch_bounds__(256 * NSUB) void k_attn(AttnArgs a) {
         for (int u = 1; u < NSUB; u++) M = fmaxf(M, run_m[u][tid]);
 #pragma unroll
         for (int u = 0; u < NSUB; u++) l += (NSUB == 1 ? 1.f : __expf(run_m[u][tid] - M)) * run_l[u][tid];
-        if (a.arrive) { st_agent(&ml[tid * 2], M); st_agent(&ml[tid * 2 + 1], l); }
-        else { ml[tid * 2] = M; ml[tid * 2 + 1] = l; }
+        ml[tid * 2] = M; ml[tid * 2 + 1] = l;
     }
     SK_STAMP(6);
     SK_STAMP_FLUSH;
-    if (!a.arrive) return;
-    // the last split of this (row, kv head) to get here combines them (sk_finish_x's order: the same bits as k_prep<true>) and leaves
-    // the planes of the group's rep x 64 columns
-    const int ns = (L + a.keys_per_split - 1) / a.keys_per_split;
-    if (!last_arriver(a.arrive + r * a.n_kv + g, ns)) return;
-    for (int e = tid; e < rep * 64; e += 256 * NSUB) {
-        const int c = g * rep * 64 + e;
-        float mv[SK_MAXSPLIT], lv[SK_MAXSPLIT], ov[SK_MAXSPLIT];
-#pragma unroll
-        for (int s = 0; s < SK_MAXSPLIT; s++) {
-            if (s < a.nsplit) {
-                const float* mlp = a.part_ml + (((size_t)s * SK_ROWS_CAP + r) * a.n_q + (c >> 6)) * 2;
-                mv[s] = ld_agent(mlp); lv[s] = ld_agent(mlp + 1);
-                ov[s] = ld_agent(a.part_o + ((size_t)s * SK_ROWS_CAP + r) * a.n_q * 64 + c);
-            }
-        }
-        float M = -INFINITY;
-#pragma unroll
-        for (int s = 0; s < SK_MAXSPLIT; s++) if (s < ns) M = fmaxf(M, mv[s]);
-        float acc = 0.f, den = 0.f;
-#pragma unroll
-        for (int s = 0; s < SK_MAXSPLIT; s++) {
-            if (s < ns) {
-                const float w = __expf(mv[s] - M);
-                den += w * lv[s];
-                acc += w * ov[s];
-            }
-        }
-        put_planes(a.pre, r, c, acc * (1.f / den));
-    }
 }
 // The same kernel on the matrix cores (fp32 accuracy: three exact bf16 planes per operand, six products; see attn_role, the form inside
 // k_step).  Grid, split layout and outputs are k_attn's.  A 64-key tile group = 4 waves x 16 keys: K rows / V rows go global -> registers
@@ -542,13 +487,12 @@ struct StoreArgs {
     // planes of next_g . x_mid in the layout the PRE kernels copy, and this block's share of every row's sum of squares (the consumer
     // sums the N / 16 shares in a fixed order and scales its OUTPUTS by the row's rstd: W (g . x) rstd = W (g . x rstd))
     const float* resid; const float* next_g; float* x_out; uint16_t* next_pre; float* next_sq;
-    // LAST (many-row down projection, split-K over gridDim.y): the last K-slice block of a column tile to finish folds the slices in index
-    // order onto the residual stream and runs the NEXT epilogue for the following layer's QKV kernel (what k_prep<false> did as a launch
-    // of its own).  arrive = [N / 16] counters, zero between launches
-    int* arrive;
+    void* reserved;                             // deliberately vestigial (nothing sets or reads it; it held the arrival counters of a removed form): without it
+                                                // sq, eps and the launch's hidden arguments move and every k_store variant's scalar loads change, the NEXT
+                                                // variant's schedule with them; to be removed by a change of its own that re-measures the 17 .. 32-row step
     const float* sq; float eps;                 // PRE operand left un-normalised by k_prep (the head's final norm): out = (W (g . x)) rsqrt(sq[row] / K + eps) (+ bias)
 };
-template <int NB, int MAXKS, bool ATT = false, bool PRE = false, bool NEXT = false, bool LAST = false>
+template <int NB, int MAXKS, bool ATT = false, bool PRE = false, bool NEXT = false>
 __global__ __launch_bounds__(256) void k_store(StoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* res = skinny_core<NB, 1, 4, MAXKS, ATT, PRE>(a.W, blockIdx.x, a.KS, a.rows, a.K, a.X, smem);
@@ -571,22 +515,8 @@ __global__ __launch_bounds__(256) void k_store(StoreArgs a) {
         float v = res[i * ld + r];
         if (PRE && a.sq) { v *= rsqrtf(a.sq[r] / (float)a.K + a.eps); asm volatile("" : "+v"(v)); }      // (rounded before the bias, as skinny_core's deferred scale)
         if (a.bias && blockIdx.y == 0) v += a.bias[n0 + i];
-        if (LAST) st_agent(&out[(size_t)r * a.N + n0 + i], v);
-        else if (NEXT) next(r, i, v + a.resid[(size_t)r * a.N + n0 + i]);
+        if (NEXT) next(r, i, v + a.resid[(size_t)r * a.N + n0 + i]);
         else out[(size_t)r * a.N + n0 + i] = v;
-    }
-    if (LAST) {
-        if (!last_arriver(a.arrive + blockIdx.x, gridDim.y)) return;
-        for (int e = threadIdx.x; e < a.rows * 16; e += blockDim.x) {
-            const int r = e >> 4, i = e & 15;
-            float v = a.resid[(size_t)r * a.N + n0 + i], pv[SK_MAXNP];
-#pragma unroll
-            for (int p = 0; p < SK_MAXNP; p++)           // all slices in flight together; folded in index order (k_prep<false>'s)
-                pv[p] = ld_agent(a.out + ((size_t)min(p, (int)gridDim.y - 1) * SK_ROWS_CAP + r) * a.N + n0 + i);
-#pragma unroll
-            for (int p = 0; p < SK_MAXNP; p++) if (p < (int)gridDim.y) v += pv[p];
-            next(r, i, v);
-        }
     }
 }
 
@@ -744,7 +674,7 @@ extern "C" int cv2_debug_chain(unsigned long long* out_host) {
 //     permlane swaps), P planes, 24 MFMAs -> the wave's partial O[head][dim]; the eight partials are merged through LDS with their
 //     (max, sum) and published as the tile's granules (o unnormalised, max, sum -- what OpAtt merges across tiles).
 // The scalar form this replaces took 3.3-4.0 us from q to the published tile (scores 1.2-1.9, softmax 0.6, PV 1.15, merge 0.35).
-// The role in three parts, so that k_step1's QA blocks can put their own q computation between the second and the third:
+// The role in two parts:
 //   att_prepare  cache rows -> registers -> planes (before q exists);   att_compute  q rows in LDS -> published tile.
 struct AttTile { bf16x8 ka[2][3]; s16x4 vb[4][3]; int n; };
 __device__ __forceinline__ void att_prepare(const float* K, const float* V, int pos, int j0, int nh, AttTile& T, char* smem) {
@@ -791,27 +721,15 @@ __device__ __forceinline__ void att_prepare(const float* K, const float* V, int 
 }
 // q rows [nh][64] sit in qs (written by this block's threads, not yet synchronised); the tile's o [nh * 64] go to granules og_o ..,
 // its (max, sum) pairs to og_ml + 2 h
-// PO_H: heads per wave in the partial-output area (8; k_step1's one-head blocks: 1).  LDSKV: the tile's cache rows were left in LDS by
-// att_dma_tile (kl / vl) instead of as planes in T -- they are turned into planes here, the keys first, the values behind the score products.
-template <int PO_H = 8, bool LDSKV = false>
-__device__ __forceinline__ void att_compute(const Gran& G, AttTile& T, int nh, unsigned og_o, unsigned og_ml, char* smem, int dbg_slot,
-                                            const char* kl = nullptr, const char* vl = nullptr) {
+__device__ __forceinline__ void att_compute(const Gran& G, AttTile& T, int nh, unsigned og_o, unsigned og_ml, char* smem, int dbg_slot) {
     float* qs = reinterpret_cast<float*>(smem);
-    float* po = qs + 16 * AT_QLD;                     // [8 waves][PO_H heads][64]
-    float* wm = po + 8 * PO_H * 64; float* wl = wm + 128;    // [8 waves][16 heads] max, sum
+    float* po = qs + 16 * AT_QLD;                     // [8 waves][8 heads][64]
+    float* wm = po + 8 * 8 * 64; float* wl = wm + 128;    // [8 waves][16 heads] max, sum
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, g4 = lane >> 4;
     const int n = T.n;
     __syncthreads();
-    if constexpr (LDSKV) {                            // key rows: row 16 w + c, 16-byte chunks 2 g4, 2 g4 + 1, 8 + 2 g4, 9 + 2 g4 (slot = chunk ^ (row & 15))
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's own DMA (it reads only the rows it fetched): long landed, but say so
-        const char* kp = kl + (size_t)(16 * w + c) * 256;
-        const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp + (((2 * g4) ^ c) << 4)), k1 = *reinterpret_cast<const f32x4*>(kp + (((2 * g4 + 1) ^ c) << 4));
-        const f32x4 k2 = *reinterpret_cast<const f32x4*>(kp + (((8 + 2 * g4) ^ c) << 4)), k3 = *reinterpret_cast<const f32x4*>(kp + (((9 + 2 * g4) ^ c) << 4));
-        planes8(k0, k1, T.ka[0][0], T.ka[0][1], T.ka[0][2]);
-        planes8(k2, k3, T.ka[1][0], T.ka[1][1], T.ka[1][2]);
-    }
     f32x4 sc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 2; s++) {
@@ -819,19 +737,6 @@ __device__ __forceinline__ void att_compute(const Gran& G, AttTile& T, int nh, u
         bf16x8 qb[3];
         planes8(*reinterpret_cast<const f32x4*>(qp), *reinterpret_cast<const f32x4*>(qp + 4), qb[0], qb[1], qb[2]);
         sc = mm6_32(sc, T.ka[s], qb);
-    }
-    if constexpr (LDSKV) {                            // value rows 16 w + 4 g4 + j, dims 16 t + c (the products above are still running)
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            f32x4 v4;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int r = 4 * g4 + j;
-                const float v = *reinterpret_cast<const float*>(vl + (size_t)(16 * w + r) * 256 + (((4 * t + (c >> 2)) ^ r) << 4) + ((c & 3) << 2));
-                v4[j] = r < n ? v : 0.f;
-            }
-            planes4(v4, T.vb[t][0], T.vb[t][1], T.vb[t][2]);
-        }
     }
     AT_T(4);
     // sc[j] = score of key kb + 4 g4 + j against head c
@@ -869,7 +774,7 @@ __device__ __forceinline__ void att_compute(const Gran& G, AttTile& T, int nh, u
         const int h = 4 * g4 + j;
         if (h < nh) {
 #pragma unroll
-            for (int t = 0; t < 4; t++) po[(w * PO_H + h) * 64 + 16 * t + c] = o[t][j];
+            for (int t = 0; t < 4; t++) po[(w * 8 + h) * 64 + 16 * t + c] = o[t][j];
         }
     }
     if (g4 == 0) { wm[w * 16 + c] = mx; wl[w * 16 + c] = ls; }
@@ -882,7 +787,7 @@ __device__ __forceinline__ void att_compute(const Gran& G, AttTile& T, int nh, u
         for (int i = 1; i < 8; i++) M = fmaxf(M, wm[i * 16 + h]);
         float acc = 0.f;
 #pragma unroll
-        for (int i = 0; i < 8; i++) acc += __expf(wm[i * 16 + h] - M) * po[(i * PO_H + h) * 64 + d];       // (wave 0 always holds a cached key: M is finite)
+        for (int i = 0; i < 8; i++) acc += __expf(wm[i * 16 + h] - M) * po[(i * 8 + h) * 64 + d];       // (wave 0 always holds a cached key: M is finite)
         G.store(og_o + tid, acc);
     }
     if (tid < nh) {
@@ -894,23 +799,6 @@ __device__ __forceinline__ void att_compute(const Gran& G, AttTile& T, int nh, u
         for (int i = 0; i < 8; i++) l += __expf(wm[i * 16 + tid] - M) * wl[i * 16 + tid];
         G.store(og_ml + tid * 2, M);
         G.store(og_ml + tid * 2 + 1, l);
-    }
-}
-// k_step1's QA blocks: the tile's 128 key rows and 128 value rows (fp32, 256 B each) go to LDS by DMA and wait THERE for q -- as planes in
-// registers (att_prepare) they would sit beside the block's 14 weight fragments per wave: 168 VGPRs, one block per CU.  One instruction =
-// 1 KiB = four rows; lane l fetches chunk (l & 15) ^ (row & 15) of row l >> 4, so that chunk c of row r lands in slot c ^ (r & 15) and both
-// fragment reads of att_compute (16 lanes: one chunk of 16 rows; or four rows x 16 consecutive dwords) touch every bank once.
-__device__ __forceinline__ void att_dma_tile(const float* K, const float* V, int j0, char* kl, char* vl) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int r = 16 * w + 4 * i + (lane >> 4);
-        const size_t off = (size_t)(j0 + r) * 64 + (((lane & 15) ^ (r & 15)) << 2);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(K + off),
-                                         (__attribute__((address_space(3))) void*)(kl + (16 * w + 4 * i) * 256), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(V + off),
-                                         (__attribute__((address_space(3))) void*)(vl + (16 * w + 4 * i) * 256), 16, 0, 0);
     }
 }
 __device__ __forceinline__ void attn_role(const Gran& G, const float* K, const float* V, int pos, int j0, int rep,
@@ -1048,169 +936,6 @@ __global__ __launch_bounds__(R1_THREADS) void k_step(StepArgs a) {
         const int ks0 = (int)(((unsigned)KS * sp) / CH_NP), ks1 = (int)(((unsigned)KS * (sp + 1)) / CH_NP);
         OpGran<8> op{&G, gl + a.off_hg, gl + a.off_hg + ks0 * 32 + 15, 0, od};
         const float v = row1_core<1, 8, 10, false, NT>(L.wdown, tile, 0, KS, a.inter, ks0, ks1, op, nullptr, 0.f, smem);
-        CH_T(1);
-        if (tid < 16) G.store(gl + a.off_dg + sp * H + tile * 16 + tid, v);
-        CH_T(2);
-    }
-}
-
-// ------------------------------------------------------------------ k_step1: round-5 experiments on the one-row step (CV2_STEP1, default off)
-// k_step's chain is x -> Q -> A -> O -> GU -> D -> x: five all-to-all hand-offs per layer, each a fabric round trip behind the slowest
-// producer.  Two restructurings, both bit-identical to k_step (every sum keeps its order: t2_finish, chain.h) and both measured NOT to pay
-// (profiles/r5_decode_step_experiments.txt); kept behind the switch as the record of the A/B, like CV2_PRE_FUSE:
-//   QA   a block per (query head, 128-key tile) computes the head's 64 q values ITSELF (the 115 KB of W_q rows requested at dispatch like
-//        every weight fragment) and goes straight on to the tile's scores: no Q -> A hand-off, no wait for the slowest of 14 q blocks.  The
-//        key / value heads of the new token keep their Q-role blocks.  The tile's cache rows wait in LDS (att_dma_tile) -- as planes in
-//        registers beside 14 weight fragments per wave the kernel needs 168 VGPRs.  372 us per step against 342: the fused block's serial
-//        work costs what the hop did, and every live tile re-reads W_q.
-//   GU2  a gate/up block covers two (gate, up) tile pairs -- 152 blocks instead of 304 -- so that more than one layer of weight requests is
-//        resident: the down projection's blocks start 4 us earlier and no longer wait for their weights, the fatter gate/up blocks publish
-//        as much later.  342.5 us against 342.4.
-// Block order per layer: Q (QA: the 2 x 2 n_kv key / value blocks only), A (QA: ntiles x 16 slots, head fastest), O, GU, D.
-#define QA_HEADS 16
-#define QA_TILE_BYTES (AT_TILE * 64 * 4)
-#define QA_ATT_BYTES ((16 * AT_QLD + 8 * 64 + 2 * 8 * 16) * 4)
-__host__ __device__ constexpr size_t qa_smem_bytes(int nks) { return 2 * (size_t)QA_TILE_BYTES + ((size_t)t2_smem_bytes(nks) > (size_t)QA_ATT_BYTES ? (size_t)t2_smem_bytes(nks) : (size_t)QA_ATT_BYTES); }
-template <bool QA, bool GU2>
-__global__ __launch_bounds__(R1_THREADS) void k_step1(StepArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int gb = blockIdx.x;
-    const int H = a.H;
-    const int nKV = 2 * 2 * a.n_kv, nQ = QA ? nKV : 2 * (a.n_q + 2 * a.n_kv), nA = QA ? a.ntiles * QA_HEADS : a.ntiles * a.n_kv, nO = H / 16,
-              nGU = GU2 ? a.inter / 32 : a.inter / 16;
-    const int per = nQ + nA + nO + nGU + CH_NP * nO;
-    const int layer = min(gb / per, a.n_layers);
-    int r = gb - layer * per;
-    const bool dbg = layer == a.dbg_layer;
-    const int r_dbg = r, od = dbg ? r : -1; (void)r_dbg; (void)dbg;
-    CH_T(0);
-    Gran G;
-    G.init(a.gran, a.gran_bytes, *a.epoch, a.err, false);
-    const unsigned gl = (unsigned)min(layer, a.n_layers - 1) * a.gl;
-    const unsigned gp = layer > 0 ? (unsigned)(layer - 1) * a.gl : 0u;
-    if (layer >= a.n_layers) {      // head
-        OpFold op{&G, gl, gl + a.off_dg, H, nullptr, -1, gl + a.off_dg + H - 1};
-        const float out = row1_core<1, 8, 4, true, true>(a.wdec, r, 0, H / 32, H, 0, H / 32, op, a.final_norm, a.eps, smem);
-        if (tid < 16) a.logits[r * 16 + tid] = out + a.bdec[r * 16 + tid];
-        return;
-    }
-    const StepLayer L = step_layer(a.layers, layer);
-    OpFold xin{&G, gp, gp + a.off_dg, H, layer == 0 ? a.xin : nullptr, od, gp + a.off_hg + a.inter - 1};
-    if (r < nQ) {                   // ---- Q (QA: only the new token's key / value heads)
-        const int head = (QA ? a.n_q : 0) + (r >> 1), half = r & 1;
-        const int pos = a.state[CV2_ST_POS];
-        const int skip = *a.dbg_skip;
-        const int f = half * 16 + ((tid >> 4) & 1) * 32 + (tid & 15);
-        const float bias = L.bqkv[head * 64 + f];
-        float c, sn;
-        auto hook = [&]() { c = a.cosT[pos * 32 + (f & 31)]; sn = a.sinT[pos * 32 + (f & 31)]; };
-        float v = row1_core<2, 4, 7, true, true>(L.wqkv, head * 4 + half, 2, H / 32, H, 0, H / 32, xin, L.ln1, a.eps, smem, hook) + bias;
-        const float vp = __shfl(v, (tid & 63) ^ 16);
-        if (head < a.n_q + a.n_kv) v = (f < 32) ? (v * c - vp * sn) : (v * c + vp * sn);
-        CH_T(1);
-        if (skip == ((layer << 16) | r) + 1) return;
-        if (tid < 32) {
-            if (head < a.n_q) G.store(gl + a.off_qg + head * 64 + f, v);
-            else if (head < a.n_q + a.n_kv) {
-                const int kvh = head - a.n_q;
-                G.store(gl + a.off_kv + kvh * 64 + f, v);
-                L.kc[((size_t)kvh * a.max_pos + pos) * 64 + f] = v;
-            } else {
-                const int kvh = head - a.n_q - a.n_kv;
-                G.store(gl + a.off_kv + (a.n_kv + kvh) * 64 + f, v);
-                L.vc[((size_t)kvh * a.max_pos + pos) * 64 + f] = v;
-            }
-        }
-        CH_T(2);
-        return;
-    }
-    r -= nQ;
-    if (r < nA) {
-        const int pos = a.state[CV2_ST_POS];
-        if constexpr (QA) {         // ---- QA: query head `head` against the 128-key tile `tile` of its kv head
-            // QA_HEADS (16) block slots per tile, the last ones empty: the blocks of one head (one per live tile) are 16 apart in the grid, i.e.
-            // on ONE XCD (consecutive block ids go round the 8 XCDs) -- they all read the head's 115 KB of W_q rows, the first from HBM, the
-            // others from that XCD's L2 (plain loads; tile-major with n_q slots and non-temporal loads the step took 398 us against 342:
-            // +4.8 MB of weight traffic per layer)
-            const int tile = r / QA_HEADS, head = r - tile * QA_HEADS;
-            if (head >= a.n_q || (tile > 0 && tile * AT_TILE >= pos)) return;
-            const int g = head / a.rep, hh = head - g * a.rep;
-            // LDS: [key rows 32 K][value rows 32 K][work: the q computation's stage / exchange / reduction, then the attention's q rows / partials]
-            char* kl = smem; char* vl = smem + QA_TILE_BYTES; char* wk = smem + 2 * QA_TILE_BYTES;
-            T2W<7> w;
-            t2_issue<7, false>(L.wqkv, head * 4, H / 32, w);
-            const float c = a.cosT[pos * 32 + (tid & 31)], sn = a.sinT[pos * 32 + (tid & 31)];
-            const float bias = L.bqkv[head * 64 + (tid & 63)];
-            const bool keys = tile * AT_TILE < pos;                          // (tile 0 at position 0: q only)
-            if (keys) att_dma_tile(L.kc + (size_t)g * a.max_pos * 64, L.vc + (size_t)g * a.max_pos * 64, tile * AT_TILE, kl, vl);
-            float v = t2_finish<7, true>(w, H / 32, H, xin, L.ln1, a.eps, wk) + bias;
-            const float vp = __shfl(v, (tid & 63) ^ 32);                     // rotate-half partner: feature f ^ 32 sits in lane f ^ 32 of wave 0
-            {   // separately rounded products and sum, as the other forms' RoPE compiles (v_mul, v_mul, v_add / v_sub; here hipcc would
-                // contract the sum into one fma: 1-ulp differences in a fifth of the q values)
-                float vc = v * c, ps = vp * sn;
-                asm volatile("" : "+v"(vc), "+v"(ps));                       // (the products leave the expression: nothing to contract)
-                v = (tid & 32) ? vc + ps : vc - ps;
-            }
-            CH_T(1);
-            __syncthreads();                                                 // the q computation's LDS is free: it becomes the attention's
-            float* qs = reinterpret_cast<float*>(wk);
-            for (int e = tid; e < 16 * AT_QLD; e += R1_THREADS) qs[e] = e < 64 ? v : 0.f;      // q row 0 (thread f < 64 holds feature f), rows 1 .. 15 zero
-            if (tid < 64 && tile == 0) G.store(gl + a.off_qg + head * 64 + tid, v);             // the O role's new-token partial needs q too
-            if (!keys) return;
-            AttTile T;
-            {
-                const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-                T.n = max(0, min(16, pos - (tile * AT_TILE + 16 * w8)));
-            }
-            const unsigned og = gl + a.off_ag + (unsigned)(tile * a.n_kv + g) * AT_GSTRIDE;
-            att_compute<1, true>(G, T, 1, og + hh * 64, og + a.rep * 64 + hh * 2, wk, od, kl, vl);
-        } else {                    // ---- A: one tile of one kv head, all its query heads (k_step's role)
-            const int tile = r / a.n_kv, g = r - tile * a.n_kv;
-            if (tile * AT_TILE >= pos) return;
-            if (layer > 0) G.wait(gp + a.off_dg + H - 1, H, CH_NP);
-            attn_role(G, L.kc + (size_t)g * a.max_pos * 64, L.vc + (size_t)g * a.max_pos * 64, pos, tile * AT_TILE, a.rep,
-                      gl + a.off_qg + g * a.rep * 64, gl + a.off_ag + (unsigned)r * AT_GSTRIDE, smem, od);
-        }
-        CH_T(2);
-        return;
-    }
-    r -= nA;
-    if (r < nO) {                   // ---- O
-        const int pos = a.state[CV2_ST_POS];
-        OpAtt op{&G, gl + a.off_ag, a.n_kv, a.rep, (pos + AT_TILE - 1) / AT_TILE, od, &xin, r * 16, gl + a.off_qg, gl + a.off_kv};
-        const float o = row1_core<1, 8, 4, false, true>(L.wo, r, 0, a.NQ / 32, a.NQ, 0, a.NQ / 32, op, nullptr, 0.f, smem);
-        CH_T(1);
-        if (tid < 16) G.store(gl + r * 16 + tid, reinterpret_cast<const float*>(smem + R1_STAGE_BYTES(a.NQ / 32))[1200 + tid] + o);
-        CH_T(2);
-        return;
-    }
-    r -= nO;
-    if (r < nGU) {                  // ---- GU
-        OpGran<4> op{&G, gl, gl + 15, 0, od};
-        if constexpr (GU2) {        // tiles 4 r .. 4 r + 3 = (gate, up) of hidden columns [32 r, 32 r + 16) and [32 r + 16, 32 r + 32)
-            T2W<7> w;
-            t2_issue<7, true>(L.wgu, r * 4, H / 32, w);
-            const float v = t2_finish<7, true>(w, H / 32, H, op, L.ln2, a.eps, smem);
-            const float u = __shfl(v, (tid & 63) + 16);            // wave 0: lanes 0..15 gate a, 16..31 up a, 32..47 gate b, 48..63 up b
-            CH_T(1);
-            if (tid < 64 && (tid & 16) == 0) G.store(gl + a.off_hg + r * 32 + (tid >> 5) * 16 + (tid & 15), (v / (1.f + __expf(-v))) * u);
-        } else {
-            const float v = row1_core<2, 4, 7, true, true>(L.wgu, r * 2, 1, H / 32, H, 0, H / 32, op, L.ln2, a.eps, smem);
-            const float u = __shfl(v, (tid & 15) + 16);
-            CH_T(1);
-            if (tid < 16) G.store(gl + a.off_hg + r * 16 + tid, (v / (1.f + __expf(-v))) * u);
-        }
-        CH_T(2);
-        return;
-    }
-    r -= nGU;
-    {                               // ---- D
-        const int sp = r / nO, tile = r - sp * nO;
-        const int KS = a.inter / 32;
-        const int ks0 = (int)(((unsigned)KS * sp) / CH_NP), ks1 = (int)(((unsigned)KS * (sp + 1)) / CH_NP);
-        OpGran<8> op{&G, gl + a.off_hg, gl + a.off_hg + ks0 * 32 + 15, 0, od};
-        const float v = row1_core<1, 8, 10, false, true>(L.wdown, tile, 0, KS, a.inter, ks0, ks1, op, nullptr, 0.f, smem);
         CH_T(1);
         if (tid < 16) G.store(gl + a.off_dg + sp * H + tile * 16 + tid, v);
         CH_T(2);
@@ -2137,9 +1862,7 @@ struct cv2_llm {
     float *attc;               // [32][n_q*64] combined attention output (many-row path)
     uint16_t *xp2;             // prepared gate/up operand written by the O projection's epilogue (xp is still being read by that launch)
     float *sqp;                // [32][hidden / 16] shares of the rows' sums of squares
-    float *sqp2;               // the same for the next layer's QKV operand (left by the down projection's last arrivers)
-    int *arrive_att, *arrive_down;   // arrival counters of the many-row path's fused combines: [32][n_kv], [hidden / 16]
-    int pre_fuse;              // CV2_PRE_FUSE=1 at creation (run_layers_pre): bit 0 the attention's combine, bit 1 the down projection's
+    float *sqp2;               // the rows' sums of squares of the QKV operand and of the head's: k_prep leaves one share per row
     uint16_t *xp, *xp_h;       // prepared operand planes [K/32][2][hi, lo][512]: k_prep output; SwiGLU output of k_gateup<2, true>
     int nsplit, keys_per_split;
     float *hbuf;               // [32][inter]
@@ -2196,8 +1919,6 @@ static size_t carve(const cv2_llm_dims& d, cv2_llm* h, char* base) {
     p = take((size_t)SK_MAXNP * 32 * d.hidden * 4); if (h) h->parts = (float*)p;
     if (h) h->chain_off = off;
     p = take(256); if (h) h->epoch = (unsigned*)p;
-    p = take((size_t)SK_ROWS_CAP * d.n_kv * 4); if (h) h->arrive_att = (int*)p;          // (zeroed at create, re-armed by their last arriver)
-    p = take((size_t)(d.hidden / 16) * 4); if (h) h->arrive_down = (int*)p;
     {   // per layer: x_mid [H], down partials [CH_NP][H], q [NQ], new key / value rows [2 n_kv 64], attention partials
         // [tiles][n_kv][AT_GSTRIDE], h [inter]
         const size_t ntiles = (d.max_pos + AT_TILE - 1) / AT_TILE;
@@ -2242,10 +1963,6 @@ extern "C" int cv2_llm_create(const cv2_llm_dims* d, const cv2_llm_weights* w, c
     h->d = *d;
     if (h->d.top_k == 0) { h->d.top_p = 0.8f; h->d.top_k = 25; h->d.win_size = 10; h->d.tau_r = 0.1f; }   // conf/cosyvoice2.yaml:33-37
     h->layers.assign(w->layers, w->layers + d->layers);
-    {
-        const char* e = getenv("CV2_PRE_FUSE");
-        h->pre_fuse = !e ? 0 : e[0] == '1' ? 3 : e[0] == 'a' ? 1 : e[0] == 'd' ? 2 : 0;
-    }
     h->w = *w;
     h->w.layers = h->layers.data();
     h->io = *io;
@@ -2427,16 +2144,11 @@ static int run_layers_pre(cv2_llm* h, int rows, const float* xin, RowMap rm, hip
     const cv2_llm_dims& d = h->d;
     const int H = d.hidden, KSH = H / 32, NQ = d.n_q * 64;
     const size_t cache_l = (size_t)d.max_seqs * d.n_kv * d.max_pos * 64;
-    // Default: 7 launches per layer, both operand preparations (k_prep) as launches of their own.  CV2_PRE_FUSE=1 / a / d at engine creation
-    // (diagnostics, kept for the A/B): the preparations done by the producers' last-arriving blocks, both / the attention's / the down
-    // projection's.  Measured on MI355X at 32 rows: 1474 / 1478 / 1287 us per step against 1292 -- the attention's seam inside the launch
-    // (drain the write-through stores, the counter's round trip, agent-coherent loads of the other splits' results, all behind the slowest
-    // split) costs ~12 us where the launch boundary with a 4.8 us k_prep costs less; the down projection's is worth what its launch was
-    // (profiles/r4_pre_fuse_ab.txt).
-    const bool fuse = h->pre_fuse & 1, fuse_d = h->pre_fuse & 2;      // ('a' / 'd': the attention's / the down projection's alone)
+    // 7 launches per layer: both operand preparations (the QKV operand's and the attention combine's) are k_prep launches of their own; the O
+    // projection's epilogue prepares the gate/up operand.  Doing them in the producers' last-arriving blocks was measured and lost
+    // (profiles/r4_pre_fuse_ab.txt), so was one unsplit attention block per (row, kv head) (profiles/r6_att_one_split.txt).
     const float* xcur = xin;
     int np = 0;
-    bool ready = false;                                  // the layer's QKV operand was left by the previous down projection (planes in xp, shares in sqp2, x1 written)
     auto prep = [&](const SkinnyX& X, int K, bool att) {
         if (att) hipLaunchKernelGGL(k_prep<true>, dim3(rows), dim3(256), 0, s, X, K, h->xp, (float*)nullptr);
         else hipLaunchKernelGGL(k_prep<false>, dim3(rows), dim3(256), 0, s, X, K, h->xp, h->sqp2);      // (one share per row: the sum of squares)
@@ -2446,30 +2158,21 @@ static int run_layers_pre(cv2_llm* h, int rows, const float* xin, RowMap rm, hip
     for (int l = 0; l < d.layers; l++) {
         const cv2_llm_layer& L = h->layers[l];
         float* x1 = (xcur == h->xa) ? h->xb : h->xa;
-        if (!ready) prep(SkinnyX{xcur, h->parts, np, L.ln1, d.rms_eps, x1}, H, false);
+        prep(SkinnyX{xcur, h->parts, np, L.ln1, d.rms_eps, x1}, H, false);
         {
             QkvArgs a{};
             a.W = L.wqkv; a.bias = L.bqkv; a.X = pre;
             a.KS = KSH; a.rows = rows; a.K = H; a.n_q = d.n_q; a.n_kv = d.n_kv;
             a.cosT = h->w.rope_cos; a.sinT = h->w.rope_sin;
             a.q = h->q; a.kc = h->kc + l * cache_l; a.vc = h->vc + l * cache_l; a.max_pos = d.max_pos; a.rm = rm;
-            a.sq = h->sqp2; a.nsq = ready ? H / 16 : 1; a.eps = d.rms_eps;     // the rows' sums of squares: the down projection's shares, or k_prep's total
+            a.sq = h->sqp2; a.nsq = 1; a.eps = d.rms_eps;     // the rows' sums of squares: k_prep's total, one share per row
             { const size_t sm = skinny_smem_bytes<2, 2, 4>(KSH); hipLaunchKernelGGL((k_qkv<2, true>), dim3(2 * (d.n_q + 2 * d.n_kv), 1), dim3(512), sm, s, a); }
         }
-        // CV2_ATT_ONE_SPLIT=1 (round 6 experiment, A/B): ONE block of four 64-key tile groups per (row, kv head) walks all the keys and leaves
-        // the O projection's operand planes itself -- no key splits, no combine launch (k_prep<true>), 64 blocks instead of ~640 + 32
-        static const bool one_split = getenv("CV2_ATT_ONE_SPLIT") && getenv("CV2_ATT_ONE_SPLIT")[0] == '1';
-        if (one_split) {
-            const int kps = (d.max_pos + 255) / 256 * 256;
-            AttnArgs a{h->q, h->kc + l * cache_l, h->vc + l * cache_l, h->att, h->att_ml, h->att_cnt, d.n_q, d.n_kv, d.max_pos, 1, kps, rm, d.n_q / d.n_kv};
-            a.arrive = h->arrive_att; a.pre = h->xp;
-            hipLaunchKernelGGL(k_attn<4>, dim3(1, d.n_kv, rows), dim3(1024), 0, s, a);
-        } else {   // attention; the last split of a (row, kv head) combines the splits and leaves the O projection's operand planes
+        {   // attention over key splits, then their combine into the O projection's operand planes
             AttnArgs a{h->q, h->kc + l * cache_l, h->vc + l * cache_l, h->att, h->att_ml, h->att_cnt, d.n_q, d.n_kv, d.max_pos, h->nsplit, h->keys_per_split, rm, d.n_q / d.n_kv};
-            if (fuse) { a.arrive = h->arrive_att; a.pre = h->xp; }
             launch_attn(a, rows, s);
         }
-        if (!fuse && !one_split) prep(SkinnyX{nullptr, h->att, h->nsplit, nullptr, 0.f, nullptr, h->att_ml, h->att_cnt}, NQ, true);
+        prep(SkinnyX{nullptr, h->att, h->nsplit, nullptr, 0.f, nullptr, h->att_ml, h->att_cnt}, NQ, true);
         float* x2 = (x1 == h->xa) ? h->xb : h->xa;
         {   // O projection; its epilogue adds the residual and prepares the gate/up operand (no k_prep launch in between)
             StoreArgs a{};
@@ -2488,19 +2191,13 @@ static int run_layers_pre(cv2_llm* h, int rows, const float* xin, RowMap rm, hip
                 hipLaunchKernelGGL((k_gateup<2, true, 2>), dim3(d.inter / 32, 1), dim3(512), sm, s, a);
             } else { const size_t sm = skinny_smem_bytes<2, 2, 4>(KSH); hipLaunchKernelGGL((k_gateup<2, true>), dim3(d.inter / 16, 1), dim3(512), sm, s, a); }
         }
-        {   // down projection, split-K; before the last layer's, the last K-slice block of a column tile finishes the residual stream
-            // and prepares the next layer's QKV operand (no k_prep launch in between)
+        {   // down projection, split-K: the partials are folded by the next layer's (or the head's) k_prep
             StoreArgs a{};
             SkinnyX preh{};
             preh.pre = h->xp_h;
             a.W = L.wdown; a.X = preh; a.KS = d.inter / 32; a.rows = rows; a.K = d.inter; a.N = H; a.out = h->parts;
             const size_t sm = skinny_smem_bytes<2, 1, 4>(cdiv(a.KS, SK_MAXNP) + 1);
-            ready = fuse_d && l + 1 < d.layers;
-            if (ready) {
-                a.resid = x2; a.next_g = h->layers[l + 1].ln1; a.x_out = (x2 == h->xa) ? h->xb : h->xa; a.next_pre = h->xp; a.next_sq = h->sqp2;
-                a.arrive = h->arrive_down;
-                hipLaunchKernelGGL((k_store<2, 10, false, true, false, true>), dim3(H / 16, SK_MAXNP), dim3(256), sm, s, a);
-            } else hipLaunchKernelGGL((k_store<2, 10, false, true>), dim3(H / 16, SK_MAXNP), dim3(256), sm, s, a);
+            hipLaunchKernelGGL((k_store<2, 10, false, true>), dim3(H / 16, SK_MAXNP), dim3(256), sm, s, a);
         }
         xcur = x2;
         np = SK_MAXNP;
@@ -2529,8 +2226,7 @@ static int init_attrs_once() {
     if (set_smem(k_qkv<1>, big) || set_smem(k_qkv<2>, big) || set_smem(k_gateup<1>, big) || set_smem(k_gateup<2>, big) ||
         set_smem((k_store<1, 8>), big) || set_smem((k_store<2, 8>), big) || set_smem((k_store<1, 8, true>), big) || set_smem((k_store<2, 8, true>), big) || set_smem((k_store<1, 10>), big) ||
         set_smem((k_store<2, 10>), big) || set_smem((k_qkv<2, true>), big) || set_smem((k_gateup<2, true>), big) || set_smem((k_gateup<2, true, 2>), big) ||
-        set_smem((k_store<2, 8, false, true>), big) || set_smem((k_store<2, 8, false, true, true>), big) || set_smem((k_store<2, 10, false, true>), big) ||
-        set_smem((k_store<2, 10, false, true, false, true>), big) || set_smem((k_step1<true, true>), big) || set_smem((k_step1<true, false>), big))
+        set_smem((k_store<2, 8, false, true>), big) || set_smem((k_store<2, 8, false, true, true>), big) || set_smem((k_store<2, 10, false, true>), big))
         return -1;
     done = true;
     return 0;
@@ -2744,20 +2440,6 @@ static int get_graph(cv2_llm* h, int n_seqs, int unroll, bool one_launch, hipGra
                 a.dbg_layer = getenv("CV2_DBG_LAYER") ? atoi(getenv("CV2_DBG_LAYER")) : 12;      // (tools/dbg_chain.py: the layer whose blocks are stamped)
 #endif
                 static const bool force_multi = getenv("CV2_CHAIN_FORCE_MULTI") != nullptr;       // diagnostics: one row through k_step<true>
-                // one row: k_step, or with CV2_STEP1 = 1 / 2 / 3 k_step1 (round 5: bit 0 QA blocks that compute their query head themselves, bit 1
-                // gate/up blocks of two tile pairs -- same ids and logits bit for bit, measured slower / equal: profiles/r5_decode_step_experiments.txt)
-                const int step1_env = getenv("CV2_STEP1") ? atoi(getenv("CV2_STEP1")) : 0;      // (read at capture: a new engine takes the current value)
-                const int step1 = step1_env & ((d.inter / 16) % 2 == 0 ? 3 : 1) & (d.n_q <= QA_HEADS ? 3 : 2);
-                if (n_seqs == 1 && !mapped && !force_multi && step1) {
-                    const bool qa = step1 & 1, gu2 = step1 & 2;
-                    const int nO = d.hidden / 16;
-                    const int per1 = (qa ? 4 * d.n_kv + a.ntiles * QA_HEADS : 2 * (d.n_q + 2 * d.n_kv) + a.ntiles * d.n_kv) + nO + (gu2 ? d.inter / 32 : d.inter / 16) + CH_NP * nO;
-                    const size_t sm1 = std::max(sm, qa ? qa_smem_bytes(d.hidden / 32) : (size_t)t2_smem_bytes(d.hidden / 32));
-                    const dim3 grid1(d.layers * per1 + d.vocab_pad / 16);
-                    if (qa && gu2) hipLaunchKernelGGL((k_step1<true, true>), grid1, dim3(R1_THREADS), sm1, cs, a);
-                    else if (qa) hipLaunchKernelGGL((k_step1<true, false>), grid1, dim3(R1_THREADS), sm1, cs, a);
-                    else hipLaunchKernelGGL((k_step1<false, true>), grid1, dim3(R1_THREADS), sm1, cs, a);
-                } else
                 if (n_seqs == 1 && !mapped && !force_multi) hipLaunchKernelGGL((k_step<false, true>), dim3(h->step_blocks), dim3(R1_THREADS), sm, cs, a);
                 else {                       // rows = slots 0 .. n - 1, or the live slots of cv2_llm_decode_rows (row -> slot map, inputs by row)
                     a.n_rows = n_seqs; a.row_slots = mapped ? h->row_slots : nullptr; a.xin = xin;
@@ -2797,31 +2479,36 @@ static int get_graph(cv2_llm* h, int n_seqs, int unroll, bool one_launch, hipGra
     return 0;
 }
 
+// one row and the device to itself: the whole step is one launch (k_step); CV2_DECODE_SHARED asks for the launches instead -- k_step
+// keeps ~1000 polling waves resident, which slows kernels of other streams running beside it more than the launches do
+static bool use_one_launch(const cv2_llm* h, int rows, int flags) {
+    static const bool shared_one = getenv("CV2_SHARED_ONE_LAUNCH") != nullptr;        // A/B switch (diagnostics): the one-launch step also beside other streams' kernels
+    return rows <= chain_rows() && h->use_chain && (shared_one || !(flags & CV2_DECODE_SHARED));
+}
+// graph replays cost ~8 us of host/queue gap each: 8 steps per replay where possible (finished slots idle inside a replay), then single steps
+static int replay_steps(cv2_llm* h, int rows, int n_steps, bool one_launch, bool mapped, hipStream_t s) {
+    constexpr int UNROLL = 8;
+    hipGraphExec_t g8 = nullptr, g1 = nullptr;
+    int i = 0;
+    if (n_steps >= UNROLL) {
+        if (get_graph(h, rows, UNROLL, one_launch, &g8, mapped)) return -1;
+        for (; i + UNROLL <= n_steps; i += UNROLL) CV2_HIP(hipGraphLaunch(g8, s));
+    }
+    if (i < n_steps) {
+        if (get_graph(h, rows, 1, one_launch, &g1, mapped)) return -1;
+        for (; i < n_steps; i++) CV2_HIP(hipGraphLaunch(g1, s));
+    }
+    return 0;
+}
+
 extern "C" int cv2_llm_decode_ex(cv2_llm* h, int32_t n_seqs, int32_t n_steps, int32_t flags, void* stream);
 extern "C" int cv2_llm_decode(cv2_llm* h, int32_t n_seqs, int32_t n_steps, void* stream) { return cv2_llm_decode_ex(h, n_seqs, n_steps, 0, stream); }
 
 extern "C" int cv2_llm_decode_ex(cv2_llm* h, int32_t n_seqs, int32_t n_steps, int32_t flags, void* stream) {
     CV2_CHECK(h, "cv2_llm_decode: null handle");
-    // one row and the device to itself: the whole step is one launch (k_step); CV2_DECODE_SHARED asks for the launches instead -- k_step
-    // keeps ~1000 polling waves resident, which slows kernels of other streams running beside it more than the launches do
-    static const bool shared_one = getenv("CV2_SHARED_ONE_LAUNCH") != nullptr;        // A/B switch (diagnostics): the one-launch step also beside other streams' kernels
-    const bool one_launch = n_seqs <= chain_rows() && h->use_chain && (shared_one || !(flags & CV2_DECODE_SHARED));
     CV2_CHECK(n_seqs >= 1 && n_seqs <= h->d.max_seqs, "cv2_llm_decode: n_seqs %d out of range", n_seqs);
     if (init_attrs_once()) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    // graph replays cost ~8 us of host/queue gap each: 8 steps per replay where possible (finished slots idle inside a replay)
-    constexpr int UNROLL = 8;
-    hipGraphExec_t g8 = nullptr, g1 = nullptr;
-    int i = 0;
-    if (n_steps >= UNROLL) {
-        if (get_graph(h, n_seqs, UNROLL, one_launch, &g8)) return -1;
-        for (; i + UNROLL <= n_steps; i += UNROLL) CV2_HIP(hipGraphLaunch(g8, s));
-    }
-    if (i < n_steps) {
-        if (get_graph(h, n_seqs, 1, one_launch, &g1)) return -1;
-        for (; i < n_steps; i++) CV2_HIP(hipGraphLaunch(g1, s));
-    }
-    return 0;
+    return replay_steps(h, n_seqs, n_steps, use_one_launch(h, n_seqs, flags), false, (hipStream_t)stream);
 }
 
 // decode over the LIVE slots only: row r of every launch serves slot slots[r].  cv2_llm_decode(n_seqs) steps slots 0 .. n_seqs - 1
@@ -2846,25 +2533,12 @@ extern "C" int cv2_llm_decode_rows(cv2_llm* h, const int32_t* slots, int32_t n_r
         sa.slots[r] = slots[r];
     }
     if (n_rows == 1 && slots[0] == 0) return cv2_llm_decode_ex(h, 1, n_steps, flags, stream);      // slot 0 alone: the one-row form of the one-launch step
-    static const bool shared_one = getenv("CV2_SHARED_ONE_LAUNCH") != nullptr;
-    const bool one_launch = n_rows <= chain_rows() && h->use_chain && (shared_one || !(flags & CV2_DECODE_SHARED));
     if (init_attrs_once()) return -1;
     hipStream_t s = (hipStream_t)stream;
     sa.n = n_rows; sa.dst = h->row_slots; sa.xnext = h->xnext; sa.xrows = h->xrows; sa.hidden = h->d.hidden;
     hipLaunchKernelGGL(k_set_rows, dim3(n_rows), dim3(256), 0, s, sa);
     CV2_LAUNCH_CHECK();
-    constexpr int UNROLL = 8;
-    hipGraphExec_t g8 = nullptr, g1 = nullptr;
-    int i = 0;
-    if (n_steps >= UNROLL) {
-        if (get_graph(h, n_rows, UNROLL, one_launch, &g8, true)) return -1;
-        for (; i + UNROLL <= n_steps; i += UNROLL) CV2_HIP(hipGraphLaunch(g8, s));
-    }
-    if (i < n_steps) {
-        if (get_graph(h, n_rows, 1, one_launch, &g1, true)) return -1;
-        for (; i < n_steps; i++) CV2_HIP(hipGraphLaunch(g1, s));
-    }
-    return 0;
+    return replay_steps(h, n_rows, n_steps, use_one_launch(h, n_rows, flags), true, s);
 }
 
 int skinny_gemm_launch(const uint16_t* w, const float* bias, const float* x, float* out, int rows, int n, int k, hipStream_t s) {

@@ -254,11 +254,10 @@ def test_hand_off_timeout_flags_every_row_of_the_launch(dev, small, n, q_block):
     assert got == want and eng.chain_broken and eng.handoff_recoveries >= 1
 
 
-@pytest.mark.parametrize('mode', ['1', '2', '3'])
-def test_one_row_step_forms_give_the_same_ids(dev, small, monkeypatch, mode):
-    """k_step (the default one-row step) against the round-5 experiments kept behind CV2_STEP1 (k_step1; 1: QA blocks that compute their
-    query head themselves and keep the tile's cache rows in LDS, 2: gate/up blocks of two tile pairs, 3: both): every sum of a row runs in
-    k_step's order in all of them, so ids AND logits are equal bit for bit (profiles/r5_decode_step_experiments.txt has their timings)."""
+def test_one_row_step_forms_give_the_same_ids(dev, small):
+    """k_step (the one-row step) on two separately created engines: every sum of a row runs in a fixed order, so the greedy ids, the RAS ids of
+    one seed AND the logits are equal bit for bit from engine to engine, and the greedy ids are the oracle's.  (The round-5 experimental
+    forms this test used to compare with k_step are gone; profiles/r5_decode_step_experiments.txt has their timings.)"""
     from cv2amd.llm import LLMEngine, MODE_RAS
     from oracle import llm as OL
     sd, sdr, _ = small
@@ -268,7 +267,6 @@ def test_one_row_step_forms_give_the_same_ids(dev, small, monkeypatch, mode):
     lg = eng.logits[0, :eng.vocab].cpu().clone()
     ras = eng.generate([req], force_len=40, mode=MODE_RAS, seed=5)[0]
     assert ids == OL.inference(sdr, *req, force_len=40)
-    monkeypatch.setenv('CV2_STEP1', mode)
     eng2 = LLMEngine(sd, dev, max_seqs=2, max_pos=512, max_out=64)
     ids2 = eng2.generate([req], force_len=40)[0]
     lg2 = eng2.logits[0, :eng2.vocab].cpu().clone()
@@ -342,18 +340,16 @@ def test_many_row_launches_normalise_like_the_other_forms(small):
     eng.park()
 
 
-def test_many_row_launches_with_fused_combines_are_reproducible(dev, small, monkeypatch):
-    """The measured-and-rejected form of the 17 .. 32-row step, kept behind CV2_PRE_FUSE=1 for the A/B (llm.hip, run_layers_pre): 5
-    launches per layer -- the attention's last split of a (row, kv head) combines the splits and leaves the O projection's operand; the
-    down projection's last K-slice block of a column tile finishes the residual stream and leaves the next QKV operand (arrival counters,
-    results read back with agent-coherent loads).  Prompts of different lengths (every row has its own split count).  Ids equal the
-    oracle's and the default form's; two runs agree bit for bit in ids AND logits (a stale read of another block's result would not)."""
+def test_many_row_launches_are_reproducible(dev, small):
+    """The 17 .. 32-row launches (llm.hip, run_layers_pre): 7 launches per layer, the key splits of the attention combined and the down
+    projection's K slices folded by k_prep launches of their own.  Prompts of different lengths (every row has its own split count).
+    Two runs on one engine agree bit for bit in ids AND logits (a stale read of another block's result would not), a second engine
+    gives the same greedy and RAS ids, and the ids equal the oracle's.  (The form that did the combines in the producers' last-arriving
+    blocks, which this test used to run, is gone; profiles/r4_pre_fuse_ab.txt has its timings.)"""
     from cv2amd.llm import LLMEngine, MODE_RAS
     from oracle import llm as OL
     sd, sdr, eng0 = small
-    monkeypatch.setenv('CV2_PRE_FUSE', '1')
     eng = LLMEngine(sd, dev, max_seqs=32, max_pos=512, max_out=64)
-    monkeypatch.delenv('CV2_PRE_FUSE')
     n = 30
     reqs = _requests(n, seed=700)
     xs = [eng.build_lm_input(*r) for r in reqs]
