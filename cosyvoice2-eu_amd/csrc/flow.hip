@@ -10,8 +10,9 @@
 //
 // Kernels (roofline that bounds each):
 //   k_gemm (gemm.h)        MFMA bf16   every Linear / Conv1d of the encoder and the estimator, fused epilogues
-//   k_attn_est             MFMA bf16   estimator self-attention, flash style (no T x T matrix in HBM); below 4 096 rows four key groups per block
-//   k_attn_est_dma         MFMA bf16   the same from 4 096 rows on, key / value tiles by LDS DMA (three stages, three waves per SIMD)
+//   k_attn_est_dma4        MFMA bf16   estimator self-attention, flash style (no T x T matrix in HBM), key / value tiles by LDS DMA: four key groups per block
+//   k_attn_est_dma         MFMA bf16   the same from 512 blocks on (257 for a full-context call without cache): one key group, two LDS stages
+//   k_attn_est             MFMA bf16   the same through registers in the plain key order: the reference the two above are tested against
 //   k_relsoftmax           HBM         conformer rel-pos softmax over explicit score matrices (encoder only, ~2 % of FLOPs)
 //   k_layernorm, k_pack, k_euler, ...  HBM   small row-wise kernels
 // Every kernel that reads or writes a 16-bit matrix operand takes its format as a trait (OP: OpBF16 / OpF16, common.h), fixed per engine by
@@ -474,29 +475,19 @@ __device__ __forceinline__ void att_est_tile(const uint16_t* Kt, const uint16_t*
     att_softmax<OP, QS, SWZ>(sacc, pf, o, mrun, lrun, kmax_q, kt, g);
     att_pv<OP, QS, SWZ>(Vt, pf, o, q16, g);
 }
-// QS query sub-tiles of 16 rows per wave, NW waves (block = 16*NW*QS rows): K / V^T fragments read from LDS once serve QS MFMAs;
-// NW = 2 doubles the block count for single-utterance calls, whose 64-row tiles would not even fill the chip once.
-// KSP = 2: a second group of NW waves works on the odd key tiles of the same queries (own LDS tiles, own register sets) and the two
-// (max, sum, O) states are merged through LDS at the end.  One utterance gives only one wave per SIMD otherwise, and every LDS /
-// MFMA / transcendental latency of the tile body is then exposed (phase stamps: ~1400 cycles of compute per 64-key tile).
-template <class OP, int QS, int NW, int KSP = 1, bool CACHE = false>
-__global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
-    __shared__ __attribute__((aligned(16))) uint16_t Ks_[KSP][2][64 * AK_LD];
-    __shared__ __attribute__((aligned(16))) uint16_t Vs_[KSP][2][64 * AV_LD];
-    const int lane = threadIdx.x & 63;
-    const int kgrp = __builtin_amdgcn_readfirstlane((int)threadIdx.x / (64 * NW));      // key group of this wave
-    const int tid = threadIdx.x - kgrp * 64 * NW, w = tid >> 6;                         // thread / wave index within the group
-    uint16_t (*Ks)[64 * AK_LD] = Ks_[kgrp];
-    uint16_t (*Vs)[64 * AV_LD] = Vs_[kgrp];
-    constexpr int RB = 16 * NW;                                  // rows per query sub-tile group
+// The REFERENCE arithmetic of the estimator attention (test hook cv2_flow_debug_attn_dma(0); no product call launches it): four waves, one
+// key group, the K / V^T tiles staged through registers into padded LDS tiles and the tile body in its plain key order
+// (att_est_tile<.., false>).  It shares no staging code, no hand-counted wait and no key permutation with the DMA kernels below, which is
+// what they are tested against.  QS query sub-tiles of 16 rows per wave (block = 64 QS rows): K / V^T fragments read from LDS once serve QS MFMAs.
+template <class OP, int QS, bool CACHE = false>
+__global__ __launch_bounds__(256) void k_attn_est(AttnEstArgs a) {
+    constexpr int NW = 4, RB = 16 * NW;                          // waves, rows per query sub-tile group
+    __shared__ __attribute__((aligned(16))) uint16_t Ks[2][64 * AK_LD];
+    __shared__ __attribute__((aligned(16))) uint16_t Vs[2][64 * AV_LD];
+    const int lane = threadIdx.x & 63, tid = threadIdx.x, w = tid >> 6;
     // grid (8 heads, query tiles): consecutive block ids go round the 8 XCDs, so XCD x serves head x only and a sequence's K / V^T of
     // that head is fetched into ONE L2 instead of all eight (r3_pmc_flow: 36 MB of fabric reads per launch before, for 6 MB of q/k/v)
-#ifdef CV2_NO_XCD        // (A/B builds: tile-major block order, every XCD sees every head)
-    const int lin_ = blockIdx.x + 8 * blockIdx.y, mt_ = gridDim.y;
-    const int m0 = (lin_ % mt_) * RB * QS, h = lin_ / mt_;
-#else
     const int m0 = blockIdx.y * RB * QS, h = blockIdx.x;
-#endif
     const int q16 = lane & 15, g = lane >> 4;
     const int s = a.seq.tile_seq[m0 >> 6];           // sequences start on 128-row boundaries: one sequence per block
     uint16_t* orow[QS];
@@ -521,7 +512,7 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
     // key source: the packed rows of this call, or the sequence's cache slot (keys 0 .. p0 + len)
     const int p0 = CACHE ? a.pos0[s] : 0;
     const int klen = p0 + len;
-    const uint16_t* kbase = nullptr; const uint16_t* vbase = nullptr; long vld = 0;      // CACHE only; the packed-row form below is the round-1 code
+    const uint16_t* kbase = nullptr; const uint16_t* vbase = nullptr; long vld = 0;      // CACHE only
     if (CACHE) {
         const long fr = a.kv_frames[s];
         kbase = a.kv[s] + a.slot * fr * 1024 + h * 64;
@@ -543,16 +534,13 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
         for (int ks = 0; ks < 2; ks++)
             qf[u][ks] = *reinterpret_cast<const v8_t<OP>*>(a.qk + (size_t)(m0 + RB * u + 16 * w + q16) * 1024 + h * 64 + ks * 32 + g * 8);
 
-    // staging: thread -> NCH K chunks (row, 16-B chunk) and NCH V^T chunks of the 64-key tile.  TWO register sets (A, B) keep the
-    // next two tiles in flight: with one set the loop ran at the latency of a tile load (~3000 cycles per 64 keys at one
-    // utterance, where only two small blocks share a CU), not at its cost.
-    constexpr int NCH = 512 / (64 * NW);
-    uint4 kregA0, kregA1, kregA2, kregA3, vregA0, vregA1, vregA2, vregA3;
-    uint4 kregB0, kregB1, kregB2, kregB3, vregB0, vregB1, vregB2, vregB3;
-    kregA2 = kregA3 = vregA2 = vregA3 = kregB2 = kregB3 = vregB2 = vregB3 = make_uint4(0u, 0u, 0u, 0u);
+    // staging: thread -> two K chunks (row, 16-B chunk) and two V^T chunks of the 64-key tile.  TWO register sets (A, B) keep the
+    // next two tiles in flight: with one set the loop ran at the latency of a tile load, not at its cost.
+    uint4 kregA0, kregA1, vregA0, vregA1;
+    uint4 kregB0, kregB1, vregB0, vregB1;
     kregA0 = kregA1 = vregA0 = vregA1 = kregB0 = kregB1 = vregB0 = vregB1 = make_uint4(0u, 0u, 0u, 0u);
 #define ATT_GLOAD1(S, C, KROW)                                                                                               \
-    if (NCH > C) {                                                                                                           \
+    {                                                                                                                        \
         const int idx = tid + 64 * NW * C, kr = idx >> 3, kc = idx & 7;                                                       \
         if (CACHE) {                                                                                                          \
             kreg##S##C = *reinterpret_cast<const uint4*>(kbase + ((KROW) - start + kr) * 512 + kc * 8);                       \
@@ -562,15 +550,15 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
             vreg##S##C = *reinterpret_cast<const uint4*>(a.vt + (size_t)(h * 64 + kr) * a.R + (KROW) + kc * 8);               \
         }                                                                                                                     \
     }
-#define ATT_GLOAD(S, KT) { const long krow_ = (long)start + (KT) * 64; ATT_GLOAD1(S, 0, krow_) ATT_GLOAD1(S, 1, krow_) ATT_GLOAD1(S, 2, krow_) ATT_GLOAD1(S, 3, krow_) }
+#define ATT_GLOAD(S, KT) { const long krow_ = (long)start + (KT) * 64; ATT_GLOAD1(S, 0, krow_) ATT_GLOAD1(S, 1, krow_) }
 #define ATT_LSTORE1(S, C, BUF)                                                                                               \
-    if (NCH > C) {                                                                                                           \
+    {                                                                                                                        \
         const int idx = tid + 64 * NW * C, kr = idx >> 3, kc = idx & 7;                                                       \
         *reinterpret_cast<uint4*>(&Ks[BUF][kr * AK_LD + kc * 8]) = kreg##S##C;                                                \
         uint2* vd = reinterpret_cast<uint2*>(&Vs[BUF][kr * AV_LD + kc * 8]);                                                  \
         vd[0] = make_uint2(vreg##S##C.x, vreg##S##C.y); vd[1] = make_uint2(vreg##S##C.z, vreg##S##C.w);                       \
     }
-#define ATT_LSTORE(S, BUF) { ATT_LSTORE1(S, 0, BUF) ATT_LSTORE1(S, 1, BUF) ATT_LSTORE1(S, 2, BUF) ATT_LSTORE1(S, 3, BUF) }
+#define ATT_LSTORE(S, BUF) { ATT_LSTORE1(S, 0, BUF) ATT_LSTORE1(S, 1, BUF) }
 
     f32x4 o[QS][4];
     float mrun[QS], lrun[QS];
@@ -583,81 +571,31 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
 
     // tile kt sits in set A for even kt, in set B for odd kt; LDS buffer = kt & 1.  The loads are unconditional (a tile index past
     // the end is clamped to the last tile) so that the number in flight is fixed and the waits stay counted.
-    // This group's tiles are kgrp, kgrp + KSP, ...; every group runs the same number of rounds (block barriers inside): a tile index
-    // past the end is loaded from the last tile and fully masked (kt_eff >= ntiles makes every key invalid).
     const int last = ntiles - 1;
-    const int rounds = (ntiles + KSP - 1) / KSP;
-    int kmask_q[QS];                                                 // kmax_q, or 0 for a tile past the end
     SK_STAMP_DECL;
     SK_STAMP(0);
-    ATT_GLOAD(A, min(kgrp, last))
-    ATT_GLOAD(B, min(kgrp + KSP, last))
+    ATT_GLOAD(A, 0)
+    ATT_GLOAD(B, min(1, last))
     SK_STAMP(1);
     // Both sets are consumed here (an empty statement the compiler has to wait in front of): hipcc issues the prologue's loads in an order
     // of its own, set A's after set B's, and the wait it places at the loop header covers the entry path too -- vmcnt(0) in EVERY
-    // iteration, i.e. a wait for the set requested half an iteration earlier instead of the one requested two tiles ago (phase stamps at
-    // one utterance: staging + wait 11 100 of a block's 23 500 cycles).  With nothing outstanding at the entry the header's wait is the
-    // back edge's: the four loads of the other set stay in flight.
-    asm volatile("" :: "v"(kregA0.x), "v"(kregA1.x), "v"(kregA2.x), "v"(kregA3.x), "v"(vregA0.x), "v"(vregA1.x), "v"(vregA2.x), "v"(vregA3.x),
-                       "v"(kregB0.x), "v"(kregB1.x), "v"(kregB2.x), "v"(kregB3.x), "v"(vregB0.x), "v"(vregB1.x), "v"(vregB2.x), "v"(vregB3.x));
-    for (int r = 0; r < rounds; r += 2) {
-        {
-            const int kt = r * KSP + kgrp;
-#pragma unroll
-            for (int u = 0; u < QS; u++) kmask_q[u] = kt < ntiles ? kmax_q[u] : 0;
-            SK_ACC(2, ATT_LSTORE(A, 0) __syncthreads());             // [2] staging incl. the wait for the tile's loads
-            ATT_GLOAD(A, min(kt + 2 * KSP, last))
-            SK_ACC(3, (att_est_tile<OP, QS>(Ks[0], Vs[0], qf, o, mrun, lrun, kmask_q, kt, q16, g)));     // [3] tile compute
-        }
-        if (r + 1 >= rounds) break;
-        {
-            const int kt = (r + 1) * KSP + kgrp;
-#pragma unroll
-            for (int u = 0; u < QS; u++) kmask_q[u] = kt < ntiles ? kmax_q[u] : 0;
-            SK_ACC(2, ATT_LSTORE(B, 1) __syncthreads());
-            ATT_GLOAD(B, min(kt + 2 * KSP, last))
-            SK_ACC(3, (att_est_tile<OP, QS>(Ks[1], Vs[1], qf, o, mrun, lrun, kmask_q, kt, q16, g)));
-        }
+    // iteration, i.e. a wait for the set requested half an iteration earlier instead of the one requested two tiles ago.  With nothing
+    // outstanding at the entry the header's wait is the back edge's: the loads of the other set stay in flight.
+    asm volatile("" :: "v"(kregA0.x), "v"(kregA1.x), "v"(vregA0.x), "v"(vregA1.x), "v"(kregB0.x), "v"(kregB1.x), "v"(vregB0.x), "v"(vregB1.x));
+    for (int kt = 0; kt < ntiles; kt += 2) {
+        SK_ACC(2, ATT_LSTORE(A, 0) __syncthreads());                 // [2] staging incl. the wait for the tile's loads
+        ATT_GLOAD(A, min(kt + 2, last))
+        SK_ACC(3, (att_est_tile<OP, QS>(Ks[0], Vs[0], qf, o, mrun, lrun, kmax_q, kt, q16, g)));         // [3] tile compute
+        if (kt + 1 >= ntiles) break;
+        SK_ACC(2, ATT_LSTORE(B, 1) __syncthreads());
+        ATT_GLOAD(B, min(kt + 3, last))
+        SK_ACC(3, (att_est_tile<OP, QS>(Ks[1], Vs[1], qf, o, mrun, lrun, kmax_q, kt + 1, q16, g)));
     }
     SK_STAMP(4);
-    if constexpr (KSP > 1) {
-        // merge: the groups 1 .. KSP - 1 park (m, l, O) in LDS (each in its own tile buffers, free now), group 0 folds them in, in group order
-        constexpr float SC = 0.125f * 1.4426950408889634f;
-        static_assert((size_t)64 * NW * QS * 18 * sizeof(float) <= sizeof(Ks_[0]), "a group's tile buffers hold its parked state");
-        __syncthreads();
-        if (kgrp != 0) {
-            float* mg = reinterpret_cast<float*>(&Ks_[kgrp][0][0]);      // [NW*64 threads][QS][18]
-#pragma unroll
-            for (int u = 0; u < QS; u++) {
-                float* d = mg + ((size_t)tid * QS + u) * 18;
-                d[0] = mrun[u]; d[1] = lrun[u];
-#pragma unroll
-                for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-                    for (int e = 0; e < 4; e++) d[2 + dt * 4 + e] = o[u][dt][e];
-            }
-        }
-        __syncthreads();
-        if (kgrp != 0) return;
-#pragma unroll
-        for (int gq = 1; gq < KSP; gq++) {
-            const float* mg = reinterpret_cast<const float*>(&Ks_[gq][0][0]);
-#pragma unroll
-            for (int u = 0; u < QS; u++) {
-                const float* d = mg + ((size_t)tid * QS + u) * 18;
-                const float m1 = d[0], l1 = d[1];
-                const float M = fmaxf(mrun[u], m1);
-                const float ms = M == -INFINITY ? 0.f : M;
-                const float a0 = __builtin_amdgcn_exp2f((mrun[u] - ms) * SC), a1 = __builtin_amdgcn_exp2f((m1 - ms) * SC);
-                lrun[u] = lrun[u] * a0 + l1 * a1;
-                mrun[u] = M;
-#pragma unroll
-                for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-                    for (int e = 0; e < 4; e++) o[u][dt][e] = o[u][dt][e] * a0 + d[2 + dt * 4 + e] * a1;
-            }
-        }
-    }
+#undef ATT_GLOAD1
+#undef ATT_GLOAD
+#undef ATT_LSTORE1
+#undef ATT_LSTORE
 #pragma unroll
     for (int u = 0; u < QS; u++) {
         float l = lrun[u];
@@ -671,38 +609,31 @@ __global__ __launch_bounds__(64 * NW * KSP) void k_attn_est(AttnEstArgs a) {
 #ifdef CV2_STAMPS
     SK_STAMP(5);
     if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
-        for (int i_ = 0; i_ < 6; i_++) g_stamps[60][i_] = st_[i_];       // slot 60: last attention launch (tools/dbg_stamps_flow.py)
+        for (int i_ = 0; i_ < 6; i_++) g_stamps[60][i_] = st_[i_];       // slot 60: last register-staged attention launch (tools/dbg_stamps_flow.py)
         g_stamps[60][6] = ntiles; g_stamps[60][7] = gridDim.x * gridDim.y;
     }
 #endif
 }
 
 // The same attention with the K / V^T tiles going global -> LDS by DMA (4 waves, one key group): no staging registers (k_attn_est keeps
-// two tiles = 64 VGPRs in flight per thread and stores them to LDS itself), LDS stages of 16 KB (round 4: three, two tiles in flight, three
-// blocks per CU; round 5: two, one tile in flight, FOUR blocks per CU at 123 VGPRs -- the loop is bound by vector issue and the L2 -> LDS
-// delivery, not by the tiles' latency: 176 -> 167 us per launch on a 32-utterance batch, profiles/r5_attention_experiments.txt).  A wave's DMA
-// instruction writes 1 KiB = 8 rows of 128 B; lane l fetches chunk (l & 7) ^ (l >> 3) of row l >> 3, so the chunk c of row r lands in
-// slot c ^ (r & 7) and the fragment reads (att_est_tile<.., true>) are conflict-free without padding.  The tile's keys are permuted among the
-// score rows (att_est_tile): same products, another order inside a k group -- agreement with k_attn_est to fp32 round-off, not bit for bit.
+// two tiles in flight in registers and stores them to LDS itself), TWO LDS stages of 16 KB: one tile in flight while the other is worked on,
+// 32 KB per block, four blocks per CU at 123 VGPRs -- the loop is bound by vector issue and the L2 -> LDS delivery, not by the tiles'
+// latency (three stages, two tiles in flight, three blocks per CU: 167 -> 176 us per launch on a 32-utterance batch,
+// profiles/r5_attention_experiments.txt; removed from the tree).  A wave's DMA instruction writes 1 KiB = 8 rows of 128 B; lane l fetches
+// chunk (l & 7) ^ (l >> 3) of row l >> 3, so the chunk c of row r lands in slot c ^ (r & 7) and the fragment reads (att_est_tile<.., true>)
+// are conflict-free without padding.  The tile's keys are permuted among the score rows (att_est_tile): same products, another order inside
+// a k group -- agreement with k_attn_est to fp32 round-off, not bit for bit.
 #ifndef ATT_STAMP_BLOCK
 #define ATT_STAMP_BLOCK 0
-#endif
-#ifndef ATT_STAGES
-#define ATT_STAGES 2     // LDS stages of the DMA attention: 2 = 32 KB per block, four blocks per CU (3: two tiles in flight, three blocks; A/B)
 #endif
 template <class OP, int QS, bool CACHE = false>
 __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
     constexpr int NW = 4, RB = 16 * NW;
-    __shared__ __attribute__((aligned(1024))) uint16_t Ks[ATT_STAGES][64 * 64];
-    __shared__ __attribute__((aligned(1024))) uint16_t Vs[ATT_STAGES][64 * 64];
+    __shared__ __attribute__((aligned(1024))) uint16_t Ks[2][64 * 64];
+    __shared__ __attribute__((aligned(1024))) uint16_t Vs[2][64 * 64];
     const int lane = threadIdx.x & 63, tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef CV2_NO_XCD
-    const int lin_ = blockIdx.x + 8 * blockIdx.y, mt_ = gridDim.y;
-    const int m0 = (lin_ % mt_) * RB * QS, h = lin_ / mt_;
-#else
     const int m0 = blockIdx.y * RB * QS, h = blockIdx.x;
-#endif
     const int q16 = lane & 15, g = lane >> 4;
     const int s = a.seq.tile_seq[m0 >> 6];
     uint16_t* orow[QS];
@@ -772,9 +703,6 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
     SK_STAMP_DECL;
     SK_STAMP(0);
     dma(0, 0);
-#if ATT_STAGES == 3
-    dma(min(1, last), 1);
-#endif
     // q fragments: loaded AFTER the first DMAs and consumed (empty asm) before the loop, so that the compiler's own wait for these loads sits
     // here -- placed at their first use inside the loop it would be a vmcnt(0) in every iteration, i.e. a wait for the DMA just issued
     v8_t<OP> qf[QS][2];
@@ -789,7 +717,6 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
         for (int ks = 0; ks < 2; ks++) asm volatile("" : "+v"(qf[u][ks]));
     int st = 0;
     SK_STAMP(1);
-#if ATT_STAGES == 2
     // two stages (32 KB of LDS: four blocks per CU instead of three): one tile in flight while the other is worked on
     for (int kt = 0; kt < ntiles; kt++) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -798,24 +725,6 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
         att_est_tile<OP, QS, true>(Ks[st], Vs[st], qf, o, mrun, lrun, kmax_q, kt, q16, g);
         st ^= 1;
     }
-#else
-    for (int kt = 0; kt < ntiles; kt++) {
-        // four DMA instructions per tile and wave, always (a tile index past the end re-fetches the last tile): tile kt has landed when at
-        // most the four of tile kt + 1 are outstanding; the barrier makes that true for every wave's share and says that every wave is
-        // done with tile kt - 1 (its fragment reads have returned: lgkmcnt), whose stage the next DMA overwrites
-        SK_TICK(ta_);
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        SK_TICK(tb_);
-        __builtin_amdgcn_s_barrier();            // (no fence: __syncthreads() would add waits of its own)
-        SK_TICK(tc_);
-        dma(min(kt + 2, last), st >= 1 ? st - 1 : 2);
-        SK_TICK(td_);
-        att_est_tile<OP, QS, true>(Ks[st], Vs[st], qf, o, mrun, lrun, kmax_q, kt, q16, g);
-        SK_TICK(te_);
-        SK_ADD(2, tb_ - ta_); SK_ADD(3, tc_ - tb_); SK_ADD(6, td_ - tc_); SK_ADD(7, te_ - td_);
-        st = st == 2 ? 0 : st + 1;
-    }
-#endif
     SK_STAMP(4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the look-ahead DMAs target this block's LDS: they land before it is released)
 #pragma unroll
@@ -837,12 +746,11 @@ __global__ __launch_bounds__(256) void k_attn_est_dma(AttnEstArgs a) {
 #endif
 }
 
-// One utterance, full context (round 5): the four-key-group form (k_attn_est<1, 4, 4>: 64 query rows x one head per 1024-thread block, group
-// g works on the key tiles g, g + 4, ..., the four states merged through LDS) with its tiles by LDS DMA like k_attn_est_dma: no staging
-// registers, no register -> LDS copies (phase stamps of the register-staged form at one utterance: staging + waits 9 800 of a block's 23 500
-// cycles), two 16 KB stages per group.  The tile body is att_est_tile<1, true> (the DMA form's key permutation): agreement with k_attn_est to
-// fp32 round-off, so -- like the other DMA forms -- it serves full-context calls only; a stream's chunk-masked recompute keeps the arithmetic
-// of its cached continuation.
+// Few blocks (one utterance, the chunks of a few streams): 64 query rows x one head per 1024-thread block, the keys split over FOUR groups of
+// four waves.  Group g works on the key tiles g, g + 4, ..., with two 16 KB LDS stages of its own fed by DMA as in k_attn_est_dma, and the four
+// (max, sum, O) states are merged through LDS in group order.  One group alone would put one wave on a SIMD at one utterance, with every
+// LDS / MFMA / transcendental latency of the tile body exposed.  The tile body is att_est_tile<1, true> (the DMA form's key permutation):
+// agreement with k_attn_est to fp32 round-off, not bit for bit.
 template <class OP, bool CACHE = false>
 __global__ __launch_bounds__(1024) void k_attn_est_dma4(AttnEstArgs a) {
     constexpr int NW = 4, KSP = 4, RB = 64;
@@ -928,7 +836,7 @@ __global__ __launch_bounds__(1024) void k_attn_est_dma4(AttnEstArgs a) {
         st ^= 1;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    // merge: the groups 1 .. 3 park (m, l, O) in their own tile buffers (free now), group 0 folds them in, in group order (k_attn_est's merge)
+    // merge: the groups 1 .. 3 park (m, l, O) in their own tile buffers (free now), group 0 folds them in, in group order
     constexpr float SC = 0.125f * 1.4426950408889634f;
     static_assert((size_t)64 * NW * 18 * sizeof(float) <= sizeof(Ts[0]), "a group's tile buffers hold its parked state");
     __syncthreads();
@@ -990,7 +898,7 @@ struct cv2_flow {
     float* tmp_t;                // [32][1024] x 3 scratch for the time MLP
     std::vector<float> t_host, dt_host;
     // row buffers
-    uint16_t *a0, *hb, *xa, *xbuf, *cat, *lnb, *qk, *vt, *att, *ff;      // bf16
+    uint16_t *a0, *hb, *xa, *xbuf, *cat, *lnb, *qk, *vt, *att;           // bf16
     float *xf, *rf, *vf, *xs, *mu, *spk, *tmpf;                           // fp32
     float *tail_part; int *tail_ticket;                                  // k_tail_panel<S > 1>: [128 panels][4 parts][16][256] partial tiles, [128] arrival counters (zero between launches)
     float *ac, *bd; uint16_t* probs; uint16_t *pos, *posp;
@@ -1030,7 +938,6 @@ static size_t flow_carve(const cv2_flow_dims& d, cv2_flow* h, char* base) {
     f.a0 = c.take<uint16_t>(RG * 320); f.hb = c.take<uint16_t>(RG * 256); f.xa = c.take<uint16_t>(RG * 256);
     f.xbuf = c.take<uint16_t>(RG * 256); f.cat = c.take<uint16_t>(RG * 512); f.lnb = c.take<uint16_t>(RG * 256);
     f.qk = c.take<uint16_t>(RG * 1024); f.vt = c.take<uint16_t>((size_t)(512 + 64) * RG); f.att = c.take<uint16_t>(RG * 512);
-    f.ff = c.take<uint16_t>(RG * 1024);
     f.tail_part = c.take<float>((size_t)128 * 4 * 16 * 256); f.tail_ticket = c.take<int>(128);
     f.xf = c.take<float>(R * 256); f.rf = c.take<float>(R * 256); f.vf = c.take<float>(R * 80); f.xs = c.take<float>(R * 80);
     f.mu = c.take<float>(R * 80); f.spk = c.take<float>((size_t)d.max_seqs * 80); f.tmpf = c.take<float>(R * 512);
@@ -1217,17 +1124,45 @@ static int est_resnet(EstCtx& c, const cv2_resnet& rn, int ridx, uint16_t* A, in
     return 0;
 }
 
-// test hook: 1 / 0 = the four-wave estimator attention with / without LDS DMA staging (agreement to fp32 round-off, see k_attn_est_dma),
-// -1 = the default (CV2_ATT_DMA)
+// test hook: 1 / -1 = the default attention forms (LDS DMA staging), 0 = the register-staged reference k_attn_est (agreement to fp32
+// round-off, see k_attn_est_dma)
 static std::atomic<int> g_att_dma{-1};
 extern "C" int cv2_flow_debug_attn_dma(int32_t on) { g_att_dma = on < 0 ? -1 : (on != 0); return 0; }
 // test hook: 1 / 0 = cv2_flow_inference replays / does not replay a hipGraph for repeated shapes, -1 = the environment (CV2_FLOW_GRAPH, default off)
 static std::atomic<int> g_flow_graph{-1};
 extern "C" int cv2_flow_debug_graph(int32_t on) { g_flow_graph = on < 0 ? -1 : (on != 0); return 0; }
 
-// transformer block; next_ln == null: last of its group -> bf16 copy of x goes to (xout, ldx).  have_qkv: the block's q / k / v^T are
-// there already (the previous block's tail kernel chained this block's QKV projection on); next_tb != null: the block that follows in the
-// group -- its QKV projection may be chained onto this block's tail (c.qkv_chained says whether it was).
+// Estimator attention.  Blocks = 8 heads x query tiles.  From ATT_QS2_MIN_BLOCKS blocks of 128 rows on (enough to fill the chip twice) the
+// one-group DMA form with two query sub-tiles per wave, from ATT_QS1_MIN_BLOCKS blocks of 64 rows on with one, below that the four-group
+// form: a 1024-thread block fills a CU, so its grid runs in two rounds above 256 blocks (one utterance of 10.2 .. 20 s: attention 13 -> 26 us
+// per launch from 2 048 to 2 304 rows), and a full-context call without cache changes to the one-group form there already
+// (ATT_QS1_MIN_BLOCKS_FULL: flow 33.5 / 36.3 / 39.3 / 41.8 ms at 1 070 / 1 310 / 1 610 / 1 910 frames -> 28.7 / 31.5 / 35.0 / 37.3).  A streaming
+// call's chunk-masked recompute and its cached continuation share the four-group form over the whole range below 512 blocks, so that
+// recomputed and cached chunks of a stream keep ONE arithmetic whatever their row counts: any other summation order moves the mel by ~3e-3
+// of its range through the 10 Euler steps.  (9 .. 15 streams' chunks, 257 .. 511 blocks, lose 1 % by it: 12 streams 167 -> 165 audio-s/s.)
+// The hook's reference (g_att_dma == 0): k_attn_est with two query sub-tiles where the default has two, with one everywhere else.
+constexpr int ATT_QS2_MIN_BLOCKS = 512, ATT_QS1_MIN_BLOCKS = 512, ATT_QS1_MIN_BLOCKS_FULL = 257;
+template <class OP, bool CACHE>
+static void est_attention_go(EstCtx& c, const AttnEstArgs& a, bool full) {
+    const int M = c.L->rows;
+    const bool ref = g_att_dma.load() == 0;
+    if (M / 128 * 8 >= ATT_QS2_MIN_BLOCKS) {
+        if (ref) hipLaunchKernelGGL((k_attn_est<OP, 2, CACHE>), dim3(8, M / 128), dim3(256), 0, c.s, a);
+        else hipLaunchKernelGGL((k_attn_est_dma<OP, 2, CACHE>), dim3(8, M / 128), dim3(256), 0, c.s, a);
+    } else if (ref) hipLaunchKernelGGL((k_attn_est<OP, 1, CACHE>), dim3(8, M / 64), dim3(256), 0, c.s, a);
+    else if (M / 64 * 8 >= (full ? ATT_QS1_MIN_BLOCKS_FULL : ATT_QS1_MIN_BLOCKS)) hipLaunchKernelGGL((k_attn_est_dma<OP, 1, CACHE>), dim3(8, M / 64), dim3(256), 0, c.s, a);
+    else hipLaunchKernelGGL((k_attn_est_dma4<OP, CACHE>), dim3(8, M / 64), dim3(1024), 0, c.s, a);
+}
+template <class OP>
+static void est_attention(EstCtx& c, const AttnEstArgs& a) {
+    if (c.inc) est_attention_go<OP, true>(c, a, false);
+    else est_attention_go<OP, false>(c, a, c.chunk <= 0);
+}
+
+// transformer block; next_ln == null: last of its group -> bf16 copy of x goes to (xout, ldx).  next_tb != null: the block that follows in
+// the group -- its QKV projection may be chained onto this block's tail (c.qkv_chained says whether it was, and the next call then finds
+// its q / k / v^T there already).
+constexpr int TAIL_ROWS2_MIN_TILES = 96;     // 64-row tiles from which the 64-row blocks serve the tail (8 streaming chunks: 192 -> 184 ms first chunk)
 template <class OP>
 static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, uint16_t* xout, long ldx, const cv2_tblock* next_tb = nullptr) {
     cv2_flow* h = c.h; const int M = c.L->rows;
@@ -1250,87 +1185,26 @@ static int est_tblock(EstCtx& c, const cv2_tblock& tb, const cv2_ln* next_ln, ui
             CV2_CHECK(bi < INC_TBLOCKS, "flow: transformer block counter overflow");
             a.kv = c.inc->kv; a.kv_frames = c.inc->kv_frames; a.pos0 = c.inc->pos0; a.slot = (long)c.step * INC_TBLOCKS + bi;
         }
-        // the four-wave forms stage their tiles by LDS DMA (k_attn_est_dma); CV2_ATT_DMA=0 (A/B, diagnostics): through registers as the two-group form
-        static const bool dma_env = !(getenv("CV2_ATT_DMA") && getenv("CV2_ATT_DMA")[0] == '0');
-        // below 4096 rows the keys are split over four wave groups of a 64-row block (one 10 s utterance: flow 26.5 -> 24.9 ms against two
-        // groups of a 32-row block; a stream's chunk alone: first chunk 51.3 -> 50.8 ms); CV2_ATT_KSP=2 (A/B, diagnostics): the two-group form
-        static const bool ksp4 = !(getenv("CV2_ATT_KSP") && getenv("CV2_ATT_KSP")[0] == '2');
-        // (without the DMA forms: two key groups of four waves put two blocks on a CU above 256 blocks; CV2_ATT_KSP=4: four groups regardless)
-        // One utterance above 2 048 packed rows (10.2 .. 20 s: 257 .. 511 blocks of the four-group form): a 1024-thread block fills a CU, so that
-        // grid ran in TWO rounds (attention 13 -> 26 us per launch from 2 048 to 2 304 rows: flow 24.6 -> 33.5 ms for 6 % more frames).  From 257
-        // blocks on the one-group DMA form runs (four 256-thread blocks per CU): 33.5 / 36.3 / 39.3 / 41.8 ms at 1 070 / 1 310 / 1 610 / 1 910
-        // frames -> 28.7 / 31.5 / 35.0 / 37.3 (two key groups of a 512-thread block, the other candidate: 30.2 / 33.0 / 36.0 / 38.7);
-        // tools/exp_flow_len.py.  Full-context calls only: a streaming call's chunk-masked recompute keeps the four-group form, the one its
-        // cached continuation runs (k_attn_est<.., CACHE>), so that recomputed and cached chunks of a stream stay bit-identical -- any other
-        // summation order moves the mel by ~3e-3 of its range through the 10 Euler steps.  CV2_ATT_DMA1_MIN=512: the round-4 threshold (A/B)
-        static const int dma1_min = getenv("CV2_ATT_DMA1_MIN") ? atoi(getenv("CV2_ATT_DMA1_MIN")) : 257;
-        static const bool dma4s = !(getenv("CV2_ATT_DMA4S") && getenv("CV2_ATT_DMA4S")[0] == '0');    // (A/B: streaming calls keep the register-staged form)
-        static const bool dma4 = !(getenv("CV2_ATT_DMA4") && getenv("CV2_ATT_DMA4")[0] == '0');      // (A/B: the register-staged four-group form)
-        static const bool ksp42 = !(getenv("CV2_ATT_KSP") && getenv("CV2_ATT_KSP")[0] == '4');
-        const int dma_dbg = g_att_dma.load();
-        const bool dma = dma_dbg < 0 ? dma_env : dma_dbg != 0;
-        if (c.inc) {
-            if (M / 128 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 2, true>), dim3(8, M / 128), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 2, 4, 1, true>), dim3(8, M / 128), dim3(256), 0, c.s, a); }
-            else if (M / 64 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 1, true>), dim3(8, M / 64), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 1, true>), dim3(8, M / 64), dim3(256), 0, c.s, a); }
-            else if (ksp4 && dma && dma4 && dma4s) hipLaunchKernelGGL((k_attn_est_dma4<OP, true>), dim3(8, M / 64), dim3(1024), 0, c.s, a);
-            else if (ksp4) hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 4, true>), dim3(8, M / 64), dim3(1024), 0, c.s, a);     // (9 .. 15 streams' chunks, 257 .. 511 blocks: two groups of a 512-thread block measured +1 %: 12 streams 165 -> 167 audio-s/s; not taken)
-            else hipLaunchKernelGGL((k_attn_est<OP, 1, 2, 2, true>), dim3(8, M / 32), dim3(256), 0, c.s, a);
-        }
-        else if (M / 128 * 8 >= 512) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 2>), dim3(8, M / 128), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 2, 4>), dim3(8, M / 128), dim3(256), 0, c.s, a); }   // enough blocks to fill the chip twice
-        else if (M / 64 * 8 >= (c.chunk > 0 ? 512 : dma1_min)) { if (dma) hipLaunchKernelGGL((k_attn_est_dma<OP, 1>), dim3(8, M / 64), dim3(256), 0, c.s, a); else hipLaunchKernelGGL((k_attn_est<OP, 1, 4>), dim3(8, M / 64), dim3(256), 0, c.s, a); }
-        // below 512 blocks: the four-group form with its tiles by LDS DMA.  Chunk-masked (streaming) calls take it together with their cached
-        // continuation (dma4s) over this whole range, so that recomputed and cached chunks of a stream keep ONE arithmetic whatever their row counts
-        else if (ksp4 && dma && dma4 && (c.chunk == 0 || dma4s)) hipLaunchKernelGGL((k_attn_est_dma4<OP, false>), dim3(8, M / 64), dim3(1024), 0, c.s, a);
-        else if (ksp4 && (M / 64 * 8 <= 256 || !ksp42 || c.chunk > 0)) hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 4>), dim3(8, M / 64), dim3(1024), 0, c.s, a);   // one utterance: the keys split over four wave groups of a 64-row block
-        else if (ksp4) hipLaunchKernelGGL((k_attn_est<OP, 1, 4, 2>), dim3(8, M / 64), dim3(512), 0, c.s, a);     // more blocks than CUs (a 1024-thread block fills one): two groups, two blocks per CU
-        else hipLaunchKernelGGL((k_attn_est<OP, 1, 2, 2>), dim3(8, M / 32), dim3(256), 0, c.s, a);       // (over two groups of a 32-row block)
+        est_attention<OP>(c, a);
     }
-    static const bool tail_rows_off = getenv("CV2_FLOW_TAIL_ROWS") && getenv("CV2_FLOW_TAIL_ROWS")[0] == '0';     // A/B switch (diagnostics)
-    static const long tail_rows_min = getenv("CV2_FLOW_TAIL_ROWS_MIN") ? atol(getenv("CV2_FLOW_TAIL_ROWS_MIN")) : 96;    // 64-row tiles from which the 64-row blocks are used (8 streaming chunks: 192 -> 184 ms first chunk)
-    if ((long)(M / 64) < 200 || !tail_rows_off) {
-        // O-projection, norm3, feed-forward and the next block's norm1 are row-local -> one launch per row panel: 16-row panels at one
-        // utterance (128 blocks), 64-row blocks for batches (every weight fragment then feeds four MFMAs)
-        TailArgs t{};
-        t.att = GB(h->att, 512); t.lda = 512;
-        t.Wo = tb.out.w; t.bo = tb.out.b; t.g3 = tb.norm3.g; t.b3 = tb.norm3.b; t.eps3 = 1e-5f;
-        t.W1 = tb.ff1.w; t.b1 = tb.ff1.b; t.W2 = tb.ff2.w; t.b2 = tb.ff2.b;
-        t.gn = next_ln ? next_ln->g : nullptr; t.bn = next_ln ? next_ln->b : nullptr; t.epsn = 1e-5f;
-        t.xf = h->xf; t.out_ln = GB(h->lnb, 256); t.ldo_ln = 256; t.out_x = xout; t.ldo_x = ldx;
-        t.seq = c.L->tab(); t.M_valid = M;
-        t.part = h->tail_part; t.ticket = h->tail_ticket;
-        t.row0 = c.inc && M > INC_LEAD ? INC_LEAD : 0;           // (cached chunks: skip the lead panels, see TailArgs::row0)
-        if ((long)(M / 64) < tail_rows_min) return tail_panel_go<OP>(t, M, c.s);
-        // batches: k_tail_rows2 (round 5); CV2_FLOW_TAIL_ROWS2=0: k_tail_rows<4>, =1: k_tail_rows2 without the chained QKV projection (A/B, diagnostics)
-        static const int rows2 = getenv("CV2_FLOW_TAIL_ROWS2") ? atoi(getenv("CV2_FLOW_TAIL_ROWS2")) : 2;
-        if (rows2 == 0) return tail_rows_go<OP>(t, M, c.s);
-        const bool chain = rows2 >= 2 && next_tb && next_ln && !c.inc;      // (cached streaming chunks file their keys / values in the QKV GEMM's epilogue)
-        if (chain) {
-            t.Wqkv = next_tb->qkv.w; t.qk = GB(h->qk, 1024); t.vt = h->vt + GUARD; t.vt_ld = h->R + GUARD + 8;
-            c.qkv_chained = true;
-        }
-        return tail_rows2_go<OP>(t, M, chain, c.s);
+    // O-projection, norm3, feed-forward and the next block's norm1 are row-local -> one launch per row panel: 16-row panels at one
+    // utterance (128 blocks), 64-row blocks for batches (every weight fragment then feeds four MFMAs)
+    TailArgs t{};
+    t.att = GB(h->att, 512); t.lda = 512;
+    t.Wo = tb.out.w; t.bo = tb.out.b; t.g3 = tb.norm3.g; t.b3 = tb.norm3.b; t.eps3 = 1e-5f;
+    t.W1 = tb.ff1.w; t.b1 = tb.ff1.b; t.W2 = tb.ff2.w; t.b2 = tb.ff2.b;
+    t.gn = next_ln ? next_ln->g : nullptr; t.bn = next_ln ? next_ln->b : nullptr; t.epsn = 1e-5f;
+    t.xf = h->xf; t.out_ln = GB(h->lnb, 256); t.ldo_ln = 256; t.out_x = xout; t.ldo_x = ldx;
+    t.seq = c.L->tab(); t.M_valid = M;
+    t.part = h->tail_part; t.ticket = h->tail_ticket;
+    t.row0 = c.inc && M > INC_LEAD ? INC_LEAD : 0;           // (cached chunks: skip the lead panels, see TailArgs::row0)
+    if (M / 64 < TAIL_ROWS2_MIN_TILES) return tail_panel_go<OP>(t, M, c.s);
+    const bool chain = next_tb && next_ln && !c.inc;         // (cached streaming chunks file their keys / values in the QKV GEMM's epilogue)
+    if (chain) {
+        t.Wqkv = next_tb->qkv.w; t.qk = GB(h->qk, 1024); t.vt = h->vt + GUARD; t.vt_ld = h->R + GUARD + 8;
+        c.qkv_chained = true;
     }
-    {
-        GemmArgs a = gemm_args(GB(h->att, 512), 512, 0, tb.out.w, M, 256, 512);
-        a.bias = tb.out.b; a.res = h->xf; a.ldres = 256; a.out_f32 = h->xf; a.ldo = 256;
-        a.ln2_g = tb.norm3.g; a.ln2_b = tb.norm3.b; a.ln2_eps = 1e-5f; a.out_ln2 = GB(h->lnb, 256); a.ldo_ln2 = 256;
-        if (est_gemm<OP>(c, a, 1)) return -1;
-    }
-    {
-        GemmArgs a = gemm_args(GB(h->ff, 1024), 1024, 0, tb.ff2.w, M, 256, 1024);
-        a.bias = tb.ff2.b; a.res = h->xf; a.ldres = 256;
-        if (next_ln) {
-            a.out_f32 = h->xf; a.ldo = 256;
-            a.ln2_g = next_ln->g; a.ln2_b = next_ln->b; a.ln2_eps = 1e-5f; a.out_ln2 = GB(h->lnb, 256); a.ldo_ln2 = 256;
-        } else {
-            a.out_bf16 = xout; a.ldo16 = ldx;
-        }
-        GemmArgs a1 = gemm_args(GB(h->lnb, 256), 256, 0, tb.ff1.w, M, 1024, 256);
-        a1.bias = tb.ff1.b; a1.act = ACT_GELU; a1.out_bf16 = GB(h->ff, 1024); a1.ldo16 = 1024;
-        if (est_gemm<OP>(c, a1, 0)) return -1;
-        if (est_gemm<OP>(c, a, 1)) return -1;
-    }
-    return 0;
+    return tail_rows2_go<OP>(t, M, chain, c.s);
 }
 
 template <class OP>

@@ -137,9 +137,6 @@ __device__ __forceinline__ void xcd_tile(int& bx, int& by) {
     const int gx = gridDim.x, T = gx * gridDim.y;
     bx = blockIdx.x; by = blockIdx.y;
     if (gridDim.z != 1 || gx == 1 || T < 16) return;
-#ifdef CV2_NO_XCD        // (A/B builds)
-    return;
-#endif
     const int L = bx + by * gx, x = L & 7, q = T >> 3, r = T & 7;
     const int Lp = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (L >> 3);
     bx = Lp % gx; by = Lp / gx;
@@ -730,188 +727,22 @@ __global__ __launch_bounds__(1024) void k_tail_panel(TailArgs a) {
 }
 constexpr size_t tail_panel_smem() { return (size_t)(17 + 8 + 32 + 6) * 1024; }
 
-// The same chain for MANY rows (batched utterances): RT row tiles of 16 rows per block, so that every weight fragment fetched from
-// L2 (1.25 MB per block) feeds RT MFMAs instead of one: at RT = 4 a block's 84 MFLOP take about as long on the CU's matrix cores as its
-// weights take through the CU's 64 B/clk vector-memory path, where the three separate GEMM launches it replaces ran at ~12 % of the MFMA
-// roof (N = 256 / K <= 1024 tiles, fp32 activations through HBM between them).  The 1024-wide hidden activations are produced and
-// consumed in four quarters of 256 columns (LDS: attention panel 16 RT KiB | x panel 8 RT | hidden quarter 8 RT), the FF2
-// accumulators stay in registers across the quarters.  Wave w owns output columns [16 w, 16 w + 16) of the N = 256 GEMMs and hidden
-// columns [16 w, 16 w + 16) of each quarter; rows: wave w finishes rows w, w + 16, ... (tile i, row w) in the row epilogues.
-template <int RT, class OP = OpBF16>
-__global__ __launch_bounds__(1024) void k_tail_rows(TailArgs a) {
-    constexpr int LDC = 260, KS0 = 16, KS1 = 8, KS2 = 32, CH = 8, QK = 8;      // QK = k-steps of one hidden quarter
-    constexpr size_t C_BYTES = (size_t)RT * 16 * LDC * 4, ATT_BYTES = (size_t)KS0 * RT * 1024;
-    constexpr size_t X_OFF = ((C_BYTES > ATT_BYTES ? C_BYTES : ATT_BYTES) + 1023) / 1024 * 1024, H_OFF = X_OFF + (size_t)KS1 * RT * 1024,
-                     PAR_OFF = H_OFF + (size_t)QK * RT * 1024;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* xs = smem + X_OFF;
-    char* hs = smem + H_OFF;
-    float* par = reinterpret_cast<float*>(smem + PAR_OFF);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m0 = blockIdx.y * (16 * RT), n = lane * 4;
-    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    {   // attention panel: piece (kb, rt) = 16 rows x 32 k; wave w fetches k-step w of every row tile
-        const int srow = lane >> 2, schunk = (lane & 3) ^ ((lane >> 5) << 1);
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++) {
-            const uint16_t* src = a.att + (long)(m0 + rt * 16 + srow) * a.lda + wave * 32 + schunk * 8;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(smem + (size_t)(wave * RT + rt) * 1024), 16, 0, 0);
-        }
-    }
-    if (wave < 6) {                                          // per-column vectors: bo, g3, b3, b2, gn, bn
-        const float* src = wave == 0 ? a.bo : wave == 1 ? a.g3 : wave == 2 ? a.b3 : wave == 3 ? a.b2 : wave == 4 ? a.gn : a.bn;
-        if (src)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(par) + wave * 1024), 16, 0, 0);
-    }
-    f32x4 xrow[RT];                                           // residual rows of this wave: row wave of every tile
-#pragma unroll
-    for (int i = 0; i < RT; i++) xrow[i] = *reinterpret_cast<const f32x4*>(a.xf + (size_t)(m0 + 16 * i + wave) * 256 + n);
-    __builtin_amdgcn_s_barrier();
-    const s16x8* wop = reinterpret_cast<const s16x8*>(a.Wo) + ((size_t)wave * KS0) * 64 + lane;
-    s16x8 wr[CH];
-#pragma unroll
-    for (int i = 0; i < CH; i++) wr[i] = wop[(size_t)i * 64];
-    int ep_start = 0, ep_len = a.M_valid;
-    if (a.seq.tile_seq) {
-        typedef int i32x4_t __attribute__((ext_vector_type(4)));
-        typedef const __attribute__((address_space(4))) i32x4_t k_i32x4;
-        const i32x4_t ti = *reinterpret_cast<k_i32x4*>(reinterpret_cast<uintptr_t>(a.seq.tile_info + (m0 >> 6)));
-        ep_start = ti.y; ep_len = ti.z;
-    }
-    vmcnt_wait<CH>();
-    __builtin_amdgcn_s_barrier();
-    const int a_off = subtile_off(lane & 15, lane >> 4);
-    const f32x4* pv = reinterpret_cast<const f32x4*>(par) + lane;
-    float* C = reinterpret_cast<float*>(smem);
-    // ---- GEMM 0: O-projection
-    f32x4 acc[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) acc[rt] = z4;
-#pragma unroll
-    for (int kb = 0; kb < KS0; kb++) {
-        const v8_t<OP> wf = __builtin_bit_cast(v8_t<OP>, wr[kb % CH]);
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++) {
-            const v8_t<OP> af = *reinterpret_cast<const v8_t<OP>*>(smem + (size_t)(kb * RT + rt) * 1024 + a_off);
-            acc[rt] = OP::mfma16(wf, af, acc[rt]);
-        }
-        if (kb + CH < KS0) wr[kb % CH] = wop[(size_t)(kb + CH) * 64];
-    }
-    // W1 fragments of the first hidden quarter: they fly during the epilogue below
-    s16x8 w1[KS1], w2[QK];
-    {
-        const s16x8* w1p = reinterpret_cast<const s16x8*>(a.W1) + ((size_t)wave * KS1) * 64 + lane;
-#pragma unroll
-        for (int i = 0; i < KS1; i++) w1[i] = w1p[(size_t)i * 64];
-    }
-    __syncthreads();                                         // attention panel fully read: its LDS becomes the C tile
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) *reinterpret_cast<f32x4*>(&C[(rt * 16 + (lane & 15)) * LDC + wave * 16 + 4 * (lane >> 4)]) = acc[rt];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < RT; i++) {   // x += o + bo ; y = LN3(x) -> x panel (bf16, operand layout of GEMM 1: tile i, row = wave)
-        const bool valid = (m0 + 16 * i + wave - ep_start) < ep_len;
-        f32x4 v = *reinterpret_cast<const f32x4*>(&C[(16 * i + wave) * LDC + n]) + pv[0] + xrow[i];
-        if (!valid) v = z4;
-        xrow[i] = v;
-        const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / 256);
-        const f32x4 d = v - mean;
-        const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 256);
-        f32x4 y = d * rsqrtf(var + a.eps3) * pv[64] + pv[128];
-        if (!valid) y = z4;
-        char* dst = xs + (size_t)((n >> 5) * RT + i) * 1024 + subtile_off(wave, (n & 31) >> 3) + (n & 7) * 2;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
-    }
-    __syncthreads();
-    // ---- feed-forward, one hidden quarter at a time; FF2 accumulates over the quarters
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) acc[rt] = z4;
-#pragma unroll
-    for (int hq = 0; hq < 4; hq++) {
-        // GEMM 1 quarter: hidden columns 256 hq + [16 w, 16 w + 16), bias + GELU -> hidden panel (operand layout of GEMM 2)
-        f32x4 a1[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++) a1[rt] = z4;
-#pragma unroll
-        for (int kb = 0; kb < KS1; kb++) {
-            const v8_t<OP> wf = __builtin_bit_cast(v8_t<OP>, w1[kb]);
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++) {
-                const v8_t<OP> xf_ = *reinterpret_cast<const v8_t<OP>*>(xs + (size_t)(kb * RT + rt) * 1024 + a_off);
-                a1[rt] = OP::mfma16(wf, xf_, a1[rt]);
-            }
-        }
-        {   // this quarter's W2 fragments (k-steps 8 hq .. 8 hq + 7 of output tile `wave`), then the next quarter's W1
-            const s16x8* w2p = reinterpret_cast<const s16x8*>(a.W2) + ((size_t)wave * KS2 + hq * QK) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < QK; i++) w2[i] = w2p[(size_t)i * 64];
-        }
-        const int cq = wave * 16 + 4 * (lane >> 4);                      // column inside the quarter
-        const f32x4 b1v = *reinterpret_cast<const f32x4*>(a.b1 + hq * 256 + cq);
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++) {
-            f32x4 v = a1[rt] + b1v;
-#pragma unroll
-            for (int e = 0; e < 4; e++) v[e] = act_apply(v[e], ACT_GELU, 0.f);
-            char* d = hs + (size_t)((cq >> 5) * RT + rt) * 1024 + subtile_off(lane & 15, (cq & 31) >> 3) + (cq & 7) * 2;
-            *reinterpret_cast<uint2*>(d) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
-        }
-        if (hq + 1 < 4) {
-            const s16x8* w1p = reinterpret_cast<const s16x8*>(a.W1) + ((size_t)((hq + 1) * 16 + wave) * KS1) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < KS1; i++) w1[i] = w1p[(size_t)i * 64];
-        }
-        __syncthreads();                                     // hidden quarter complete
-#pragma unroll
-        for (int kb = 0; kb < QK; kb++) {
-            const v8_t<OP> wf = __builtin_bit_cast(v8_t<OP>, w2[kb]);
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++) {
-                const v8_t<OP> hf = *reinterpret_cast<const v8_t<OP>*>(hs + (size_t)(kb * RT + rt) * 1024 + a_off);
-                acc[rt] = OP::mfma16(wf, hf, acc[rt]);
-            }
-        }
-        __syncthreads();                                     // hidden panel consumed: the next quarter may overwrite it
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) *reinterpret_cast<f32x4*>(&C[(rt * 16 + (lane & 15)) * LDC + wave * 16 + 4 * (lane >> 4)]) = acc[rt];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < RT; i++) {   // x += ff + b2 ; stores
-        const int m = m0 + 16 * i + wave;
-        const bool valid = (m - ep_start) < ep_len;
-        f32x4 v = *reinterpret_cast<const f32x4*>(&C[(16 * i + wave) * LDC + n]) + pv[192] + xrow[i];
-        if (!valid) v = z4;
-        if (a.gn) {
-            *reinterpret_cast<f32x4*>(a.xf + (size_t)m * 256 + n) = v;
-            const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / 256);
-            const f32x4 d = v - mean;
-            const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 256);
-            f32x4 y = d * rsqrtf(var + a.epsn) * pv[256] + pv[320];
-            if (!valid) y = z4;
-            *reinterpret_cast<uint2*>(a.out_ln + (size_t)m * a.ldo_ln + n) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
-        } else {
-            *reinterpret_cast<uint2*>(a.out_x + (size_t)m * a.ldo_x + n) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
-        }
-    }
-}
-// ---- round 5: the same chain with 32-column wave tiles and ONE weight stream (k_tail_rows2)
-// k_tail_rows<4> spends ~1 400 cycles per 32-wide k-step where its matrix-core work is 256: 16 waves x (16 columns x 64 rows) re-read the
-// block's four activation row tiles from LDS once per 16 columns (64 KB per k-step = 512 cycles of LDS bandwidth), every GEMM of the chain
-// starts with its weight fragments' L2 round trip exposed, and every phase ends in a block barrier with all 16 waves in step.  Here:
+// ---- the same chain for MANY rows (batched utterances): k_tail_rows2, 64-row blocks
+// Four row tiles of 16 rows per block, so that every weight fragment fetched from L2 (1.25 MB per block) feeds four MFMAs instead of one:
+// a block's 84 MFLOP then take about as long on the CU's matrix cores as its weights take through the CU's 64 B/clk vector-memory path.
+// The 1024-wide hidden activations are produced and consumed in four quarters of 256 columns, the FF2 accumulators stay in registers
+// across the quarters.
 //   * 8 waves, wave w owns columns [32 w, 32 w + 32) x 64 rows: two weight fragments and four activation fragments feed eight MFMAs, so a
 //     k-step moves 32 KB through LDS (256 cycles), 16 KB of weights through the CU's vector-memory path (256 cycles) and holds the matrix
-//     cores 256 cycles -- balanced instead of LDS-bound;
+//     cores 256 cycles -- balanced (16 waves x 16 columns re-read the four activation row tiles once per 16 columns: 64 KB per k-step,
+//     LDS-bound at ~1 400 cycles per k-step);
 //   * the block's GEMMs (O projection, 4 x {FF1 quarter, FF2 quarter}, optionally six 256-column tiles of the next block's QKV projection)
 //     are ONE sequence for the weight ring: a slot freed at k-step kb is refilled with the fragment 8 k-steps on, whichever GEMM that
 //     belongs to, so the stream runs through the epilogues and barriers;
 //   * the hidden quarters are double-buffered (in the LDS of the attention panel, dead by then): one barrier per quarter, FF2 of quarter
 //     q and FF1 of quarter q + 1 run back to back, and the two waves of a SIMD drift apart (one in GELU, one in MFMAs).
-// Every sum keeps k_tail_rows<4>'s order (k-steps in order in one accumulator per output tile), the epilogue expressions are the same:
-// the results are bit-identical to it (tests/test_flow_gpu.py), and the chained QKV projection is k_gemm's sum (8 k-steps in order).
+// Summation order: every GEMM adds its 32-wide k-steps in order into ONE fp32 accumulator per 16 x 16 output tile; FF2 runs over the hidden
+// quarters in order (k-steps 0 .. 31 of its K = 1024) in the same accumulator; the chained QKV projection is k_gemm's sum (8 k-steps in order).
 #define TR2_CH 8
 struct Tr2Ring { s16x8 r0[TR2_CH], r1[TR2_CH]; };
 // fragment `frag` (1 KiB) behind a wave-uniform pointer, this lane's 16 bytes: scalar base + ONE per-lane byte offset (written as
@@ -944,15 +775,6 @@ __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x
     v8_t<OP> af[2][4];
 #pragma unroll
     for (int rt = 0; rt < 4; rt++) af[0][rt] = *reinterpret_cast<const v8_t<OP>*>(panel + (size_t)rt * 1024 + a_off);
-#ifdef TR2_DIAG_MFMA32
-    // TIMING-ONLY diagnostic (round 6, the round-5 review's item 4a; results are numerically meaningless): the k-step's eight
-    // v_mfma_f32_16x16x32_bf16 (each holds the SIMD's vector issue 8 of its 16 cycles) replaced by four v_mfma_f32_32x32x16_bf16 (8 of 32)
-    // on the SAME operand and accumulator registers -- same matrix-core time, same LDS / weight traffic, half the issue cycles taken from the
-    // GELU that rides beside them.  What the feed-forward phase would gain from 32 x 32 tiles, before any layout is rewritten.
-    f32x16 t32a, t32b;
-#pragma unroll
-    for (int i = 0; i < 16; i++) { t32a[i] = acc[0][i >> 2][i & 3]; t32b[i] = acc[1][i >> 2][i & 3]; }
-#endif
 #pragma unroll
     for (int kb = 0; kb < NKS; kb++) {
         const int sl = (PH + kb) % TR2_CH;
@@ -962,29 +784,12 @@ __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x
             for (int rt = 0; rt < 4; rt++) af[(kb + 1) & 1][rt] = *reinterpret_cast<const v8_t<OP>*>(panel + (size_t)((kb + 1) * 4 + rt) * 1024 + a_off);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef TR2_DIAG_MFMA32
-        t32a = OP::mfma32(f0, af[kb & 1][0], t32a);
-        t32b = OP::mfma32(f1, af[kb & 1][1], t32b);
-        t32a = OP::mfma32(f0, af[kb & 1][2], t32a);
-        t32b = OP::mfma32(f1, af[kb & 1][3], t32b);
-        side(kb);
-        asm volatile("" : "+v"(t32a), "+v"(t32b));
-        if (kb + TR2_CH < NKS) { R.r0[sl] = tr2_ld(w0, kb + TR2_CH, lane16); R.r1[sl] = tr2_ld(w1, kb + TR2_CH, lane16); }
-        else if (NNKS > 0 && kb + TR2_CH - NKS < NNKS) { R.r0[sl] = tr2_ld(nw0, kb + TR2_CH - NKS, lane16); R.r1[sl] = tr2_ld(nw1, kb + TR2_CH - NKS, lane16); }
-        __builtin_amdgcn_sched_barrier(0);
-        continue;
-#endif
 #pragma unroll
         for (int rt = 0; rt < 4; rt++) {
-#ifndef TR2_DIAG_NOMFMA
             acc[0][rt] = SWAP ? OP::mfma16(af[kb & 1][rt], f0, acc[0][rt])
                               : OP::mfma16(f0, af[kb & 1][rt], acc[0][rt]);
             acc[1][rt] = SWAP ? OP::mfma16(af[kb & 1][rt], f1, acc[1][rt])
                               : OP::mfma16(f1, af[kb & 1][rt], acc[1][rt]);
-#else
-            acc[0][rt] += __builtin_bit_cast(f32x4, f0) + __builtin_bit_cast(f32x4, af[kb & 1][rt]);
-            acc[1][rt] += __builtin_bit_cast(f32x4, f1);
-#endif
         }
         side(kb);
         // (both column tiles' accumulator chains pass through one opaque statement per k-step: hipcc otherwise runs tile 0's chain over all
@@ -995,10 +800,6 @@ __device__ __forceinline__ void tr2_gemm(Tr2Ring& R, const s16x8* w0, const s16x
         else if (NNKS > 0 && kb + TR2_CH - NKS < NNKS) { R.r0[sl] = tr2_ld(nw0, kb + TR2_CH - NKS, lane16); R.r1[sl] = tr2_ld(nw1, kb + TR2_CH - NKS, lane16); }
         __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef TR2_DIAG_MFMA32
-#pragma unroll
-    for (int i = 0; i < 16; i++) { acc[0][i >> 2][i & 3] = t32a[i]; acc[1][i >> 2][i & 3] = t32b[i]; }
-#endif
 }
 template <bool QKV, class OP = OpBF16>
 __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
@@ -1096,7 +897,7 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
         *reinterpret_cast<uint2*>(dst) = make_uint2(OP::pack2(y[0], y[1]), OP::pack2(y[2], y[3]));
     }
     TR2_BARRIER;                                         // x panel complete; the C tile is consumed: its LDS becomes the hidden quarters
-    // ---- feed-forward, one hidden quarter at a time; FF2 accumulates over the quarters (in order: the sums are k_tail_rows<4>'s).  The
+    // ---- feed-forward, one hidden quarter at a time; FF2 accumulates over the quarters, in order.  The
     // GELU of a quarter is the block's largest VALU item (32 values per thread: ~7 000 cycles per quarter beside 4 400 of MFMAs when it runs
     // on its own): quarter q's GELU rides on the k-steps of FF2(q - 1) -- one accumulator tile per k-step -- so only quarter 0's is exposed.
     // GEMM order for the weight ring: FF1(0), FF1(1), FF2(0), FF1(2), FF2(1), FF1(3), FF2(2), FF2(3)[, QKV tiles]; every one 8 k-steps, phase 0.
@@ -1107,10 +908,8 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
         char* hs = smem + (size_t)(hq & 1) * 32 * 1024;
         const int cq = wave * 32 + c * 16 + 4 * (lane >> 4);
         f32x4 v = acc[c][rt] + b1v[c];
-#ifndef TR2_DIAG_NOGELU                                     // (diagnostic builds: where does the feed-forward phase spend its time?)
 #pragma unroll
         for (int e = 0; e < 4; e++) v[e] = act_apply(v[e], ACT_GELU, 0.f);
-#endif
         char* d = hs + (size_t)((cq >> 5) * RT + rt) * 1024 + subtile_off(lane & 15, (cq & 31) >> 3) + (cq & 7) * 2;
         *reinterpret_cast<uint2*>(d) = make_uint2(OP::pack2(v[0], v[1]), OP::pack2(v[2], v[3]));
     };
@@ -1227,12 +1026,6 @@ __global__ __launch_bounds__(512) void k_tail_rows2(TailArgs a) {
     SK_STAMP_FLUSH_RING(((unsigned long long)0x7A11 << 32) | 1536u, ((unsigned long long)64 << 48) | ((unsigned long long)32 << 32) | (unsigned)gridDim.y);
 }
 constexpr size_t tail_rows2_smem() { return (size_t)(68 + 32 + 6) * 1024; }
-
-template <int RT>
-constexpr size_t tail_rows_smem() {
-    constexpr size_t c = (size_t)RT * 16 * 260 * 4, att = (size_t)16 * RT * 1024;
-    return ((c > att ? c : att) + 1023) / 1024 * 1024 + (size_t)(8 + 8) * RT * 1024 + 6 * 1024;
-}
 
 template <int BM, int BN, bool SPLITA = false, int NSTAGE = 2>
 constexpr size_t gemm_smem_bytes() {

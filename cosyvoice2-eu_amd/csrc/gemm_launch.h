@@ -56,17 +56,7 @@ static int gemm_go_panel(const GemmArgs& a, int batch, hipStream_t s) {
     }
 }
 
-// many rows: 64-row blocks (M is a multiple of 128)
-template <class OP = OpBF16>
-static int tail_rows_go(const TailArgs& a, int M, hipStream_t s) {
-    constexpr size_t sm = tail_rows_smem<4>();
-    static std::atomic<bool> once{false};    // idempotent attribute call: a second thread repeats it rather than launch before it is in place
-    if (!once) { CV2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tail_rows<4, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm)); once = true; }
-    hipLaunchKernelGGL((k_tail_rows<4, OP>), dim3(1, M / 64, 1), dim3(1024), sm, s, a);
-    CV2_LAUNCH_CHECK();
-    return 0;
-}
-// round 5: 8 waves x (32 columns x 64 rows), one weight stream through the block's GEMMs; qkv: the next block's QKV projection chained on
+// many rows: 64-row blocks (M is a multiple of 128), 8 waves x (32 columns x 64 rows), one weight stream through the block's GEMMs; qkv: the next block's QKV projection chained on
 template <class OP = OpBF16>
 static int tail_rows2_go(const TailArgs& a, int M, bool qkv, hipStream_t s) {
     constexpr size_t sm = tail_rows2_smem();
@@ -92,11 +82,8 @@ static int tail_panel_go(const TailArgs& a, int M, hipStream_t s) {
         once = true;
     }
     // fewer panels than CUs: split the feed-forward's hidden columns over 2 or 4 workgroups per panel (needs the scratch of TailArgs)
-    static const int split_env = getenv("CV2_FLOW_TAIL_SPLIT") ? atoi(getenv("CV2_FLOW_TAIL_SPLIT")) : -1;      // A/B switch (diagnostics): 1 / 2 / 4
     const int panels = (M - a.row0) / 16;
-    int S = a.part ? (panels <= 64 ? 4 : (panels <= 128 ? 2 : 1)) : 1;
-    // the scratch holds 128 panels x 4 parts and 128 tickets: a forced split only where it fits, else the default for this panel count
-    if (split_env > 0 && a.part && (split_env == 1 || ((split_env == 2 || split_env == 4) && panels <= 128))) S = split_env;
+    const int S = a.part ? (panels <= 64 ? 4 : (panels <= 128 ? 2 : 1)) : 1;        // (the scratch holds 128 panels x 4 parts and 128 tickets)
     if (S == 4) hipLaunchKernelGGL((k_tail_panel<4, OP>), dim3(4, panels, 1), dim3(1024), sm, s, a);
     else if (S == 2) hipLaunchKernelGGL((k_tail_panel<2, OP>), dim3(2, panels, 1), dim3(1024), sm, s, a);
     else hipLaunchKernelGGL((k_tail_panel<1, OP>), dim3(1, panels, 1), dim3(1024), sm, s, a);

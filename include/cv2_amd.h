@@ -331,10 +331,12 @@ int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, const cv2_fl
  * same `gen` as the source.  The source must hold exactly n_frames (its tails belong to that position). */
 int cv2_flow_cache_copy(const cv2_flow* h, const void* src, int32_t src_frames, void* dst, int32_t dst_frames, int32_t n_frames, void* stream);
 
-/* Test hook: 1 / 0 = the estimator attention of large batches (>= 4096 rows) with / without LDS DMA staging of its key / value tiles
- * (the DMA form permutes a tile's keys among the score rows: the same products summed in another order inside a matrix-core k group --
- * the two forms agree to fp32 round-off, 3-4e-3 of the mel range after the 10 Euler steps, NOT bit for bit; batches of >= 4096 rows
- * therefore differ from the same utterances run alone by that margin), -1 = the default. */
+/* Test hook: 1 or -1 = the default forms of the estimator attention (key / value tiles by LDS DMA: one key group from 512 blocks of
+ * 8 heads x 64 query rows on -- 257 for a full-context call without cache --, four key groups below), 0 = the reference: one
+ * register-staged kernel with one key group at every size.  The DMA forms permute a tile's keys among the score rows (the same products
+ * summed in another order inside a matrix-core k group) and the four-group form sums the key tiles in four interleaved partial states:
+ * default and reference agree to fp32 round-off, 3-4e-3 of the mel range after the 10 Euler steps, NOT bit for bit.  For the same reason
+ * a batch that crosses a block-count switch differs from the same utterances run alone by that margin. */
 int cv2_flow_debug_attn_dma(int32_t on);
 /* Test hook: 1 = cv2_flow_inference captures the launches of a call into a hipGraph at the second use of a shape (token / prompt lengths, flags)
  * and replays it from then on (bit-identical results; CV2_FLOW_GRAPH=1), 0 = always the launches, -1 = the environment (default off: measured

@@ -175,8 +175,8 @@ def test_repeated_shapes_replay_one_graph_bit_identically(eng):
 
 
 def test_large_batch_tile_configurations_agree_with_single(dev, flow_sd):
-    """Eight ~10 s utterances packed together select the large-grid kernels (k_gemm<64,256,2,4>, <128,128,2,4>, k_attn_est<2,4>);
-    one utterance alone runs on the row-panel GEMM, the 64x128 tiles and the key-split attention that the golden-vector tests
+    """Eight ~10 s utterances packed together select the large-grid kernels (k_gemm<64,256,2,4>, <128,128,2,4>, k_attn_est_dma<2>);
+    one utterance alone runs on the row-panel GEMM, the 64x128 tiles and the key-split attention (k_attn_est_dma4) that the golden-vector tests
     cover.  Same arithmetic class (bf16 operands, fp32 accumulate), different summation order: agreement to bf16 round-off
     after the 10 Euler steps, not bit equality."""
     from cv2amd import synth
@@ -197,12 +197,14 @@ def test_large_batch_tile_configurations_agree_with_single(dev, flow_sd):
 
 
 def test_attention_with_dma_staged_tiles_agrees_with_the_register_staged_form(dev, flow_sd):
-    """Batches of >= 4096 / 8192 rows run the estimator attention with its key / value tiles staged by LDS DMA (k_attn_est_dma<1> / <2>:
-    swizzled 128-byte rows, three stages, inline-asm DMA with hand-counted waits, the keys of a tile permuted among the score rows so that
-    the V^T operand is one 16-byte read).  Same products as the register-staged form (test hook cv2_flow_debug_attn_dma), another order
-    inside a matrix-core k group: the mels agree to round-off amplified by the 10 Euler steps -- the class of the batch-vs-single test
-    above -- in full context, under chunk masks, and in the cached streaming form (keys / values from the streams' caches, second call at
-    pos0 > 0)."""
+    """Every default form of the estimator attention stages its key / value tiles by LDS DMA (k_attn_est_dma<1> / <2> from 512 blocks on,
+    the four-key-group k_attn_est_dma4 below: swizzled 128-byte rows, two stages, inline-asm DMA with hand-counted waits, the keys of a
+    tile permuted among the score rows so that the V^T operand is one 16-byte read).  The reference (test hook cv2_flow_debug_attn_dma(0))
+    is ONE register-staged kernel with one key group, k_attn_est<1> / <2>.  Same products, another order inside a matrix-core k group;
+    below 512 blocks the summation order over the key tiles differs as well (four interleaved partial states merged at the end, against one
+    running state).  The mels agree to round-off amplified by the 10 Euler steps -- the class of the batch-vs-single test above, which
+    changes the summation order of every GEMM too -- in full context, under chunk masks, and in the cached streaming form (keys / values
+    from the streams' caches, second call at pos0 > 0)."""
     from cv2amd import synth, lib as L
     from cv2amd.flow import FlowEngine
     big = FlowEngine(flow_sd, dev, max_utts=16, max_len=1200)

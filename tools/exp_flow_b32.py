@@ -1,5 +1,5 @@
-"""Flow stage alone on a configs[2]-like batch (32 ragged utterances), the estimator attention with / without LDS DMA staging of its
-key / value tiles (test hook cv2_flow_debug_attn_dma):  python tools/exp_flow_b32.py [n_utts]"""
+"""Flow stage alone on a configs[2]-like batch (32 ragged utterances): the default estimator attention (key / value tiles by LDS DMA)
+against the register-staged reference kernel k_attn_est (test hook cv2_flow_debug_attn_dma):  python tools/exp_flow_b32.py [n_utts]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'cosyvoice2-eu_amd'))
