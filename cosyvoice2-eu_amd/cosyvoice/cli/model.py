@@ -41,6 +41,7 @@ from cv2amd import lib as L
 from cv2amd import stretch as S
 from cv2amd import outrate as O
 from cv2amd import sampling as SP
+from cv2amd import solver as SV
 
 
 class _FairLock:
@@ -153,6 +154,7 @@ class CosyVoice2Model:
         self.stretch_dict = {}                 # uuid -> _Stretcher of a streaming call with speed != 1; created and dropped with hift_cache_dict[uuid]
         self.out_dict = {}                     # uuid -> _Out of a call with output_sample_rate / pcm16; created and dropped with hift_cache_dict[uuid]
         self.samp_dict = {}                    # uuid -> [Sampling, vocoder invocations so far] of a call with its own sampler settings / seed; likewise
+        self.solver_dict = {}                  # uuid -> cv2amd.solver.Solver of a call with its own flow steps / guidance rate; likewise
         self._hift_pin, self._pin_rr = {}, -1  # uuid -> index of the HiftPool engine / HIP stream serving that call's chunks
         self.llm_stream = torch.cuda.Stream(self.device)   # (torch.cuda.Stream.priority_range() is (0, -1) here: no priority below the default exists)
         self.sampling_mode = MODE_RAS if sampling == 'ras' else MODE_GREEDY
@@ -231,8 +233,19 @@ class CosyVoice2Model:
     def token2wav(self, token, prompt_token, prompt_feat, embedding, token_offset, uuid, stream=False, finalize=False, speed=1.0):
         tts_mel, _ = self.flow.inference(token=token, token_len=None, prompt_token=prompt_token, prompt_token_len=None,
                                          prompt_feat=prompt_feat, prompt_feat_len=None, embedding=embedding, streaming=stream,
-                                         finalize=finalize)
+                                         finalize=finalize, **self._solver_kw([uuid]))
         return self._mel2wav(tts_mel, token_offset, uuid, finalize, speed)
+
+    def _solver_kw(self, uuids):
+        """The `solver=` keyword of a flow call that serves these calls: nothing when none of them carries solver settings (the call
+        without them is exactly the call before they existed)."""
+        sv = [self.solver_dict.get(u) for u in uuids]
+        return {} if all(v is None for v in sv) else {'solver': sv}
+
+    def _steps(self, uuid):
+        """the Euler steps the call's flow runs (one flow launch has one step count: the scheduler groups by it)"""
+        sv = self.solver_dict.get(uuid)
+        return self.flow.n_timesteps if sv is None or sv.steps is None else sv.steps
 
     def _vocoder_seed(self, uuid):
         """The noise seed of the call's next vocoder invocation: hift_seed(seed, segment, 0, 1, 2, ...) for a call that carries a seed
@@ -471,17 +484,17 @@ class CosyVoice2Model:
                 self._prompt_caches.move_to_end(c.pkey)
                 fc = self._flow_caches[c.uuid] = self.flow.clone_cache(pc, cap)
             else:
-                fc = self._flow_caches[c.uuid] = self.flow.new_cache(cap)
+                fc = self._flow_caches[c.uuid] = self.flow.new_cache(cap, **({'solver': self.solver_dict[c.uuid]} if c.uuid in self.solver_dict else {}))
         return fc
 
-    def _build_prompt_cache(self, pkey, fpt, feat, femb):
+    def _build_prompt_cache(self, pkey, fpt, feat, femb, solver=None):
         """Background: the flow cache of a prompt alone (its whole chunks), kept for later calls with the same prompt — their first
         chunk then computes ~100 frames instead of the prompt's ~500 + its own.  At most `prompt_cache_max` prompts are kept (LRU)."""
         try:
             torch.cuda.set_device(self.device)
             with self.run_lock:
                 if pkey not in self._prompt_caches:
-                    pc = self.flow.prompt_cache(fpt, feat, femb, hop=self.token_hop_len)
+                    pc = self.flow.prompt_cache(fpt, feat, femb, hop=self.token_hop_len, **({} if solver is None else {'solver': solver}))
                     torch.cuda.current_stream().synchronize()
                     if pc is not None:
                         self._prompt_caches[pkey] = pc
@@ -493,7 +506,7 @@ class CosyVoice2Model:
             self._prompt_building.discard(pkey)
 
     def _flow_batch(self, grp, streaming, finalize):
-        """[(mel, first frame index)] of one group of chunks.  Non-final chunks of streaming calls go through the per-call flow cache
+        """[(mel, first frame index)] of one group of chunks (guidance rates may differ inside a launch; step counts split the flow calls only).  Non-final chunks of streaming calls go through the per-call flow cache
         when that pays: never a call's first chunk (its latency is the one that is felt; the second chunk fills the cache instead),
         and only when at least `flow_cache_min_group` chunks share the round or a prefix is long — one short stream alone is
         latency-bound either way (measured: 45 ms per chunk cached, 37 ms recomputed; 8 streams: 87 ms against 127 ms per round).  A
@@ -513,14 +526,16 @@ class CosyVoice2Model:
                 for c in grp:                                                  # several streams at once and a prompt not seen before:
                     if c.offset == 0 and c.pkey is not None and c.pkey not in self._prompt_caches and c.pkey not in self._prompt_building:
                         self._prompt_building.add(c.pkey)                      # prepare it for the calls to come: started when this round
-                        self._builds_due.append((c.pkey, c.fpt, c.feat, c.femb))   # has delivered (its waiters are in line for the device first)
-        if cached:
-            res = self.flow.inference_chunk_batch([utts[i] for i in cached], [self._flow_cache_for(grp[i]) for i in cached], finalize=False)
-            for i, r in zip(cached, res):
+                        self._builds_due.append((c.pkey, c.fpt, c.feat, c.femb, self.solver_dict.get(c.uuid)))   # has delivered (its waiters are in line for the device first)
+        for n in sorted({self._steps(grp[i].uuid) for i in cached}):           # one flow launch has one Euler step count (the vocoder below
+            sub = [i for i in cached if self._steps(grp[i].uuid) == n]         # still serves the whole group)
+            res = self.flow.inference_chunk_batch([utts[i] for i in sub], [self._flow_cache_for(grp[i]) for i in sub], finalize=False,
+                                                  **self._solver_kw([grp[i].uuid for i in sub]))
+            for i, r in zip(sub, res):
                 outs[i] = r
         rest = [i for i in range(len(grp)) if outs[i] is None]
         if rest:
-            res = self.flow.inference_batch([utts[i] for i in rest], streaming=streaming, finalize=finalize)
+            res = self.flow.inference_batch([utts[i] for i in rest], streaming=streaming, finalize=finalize, **self._solver_kw([grp[i].uuid for i in rest]))
             for i, m in zip(rest, res):
                 outs[i] = (m, 0)
         return outs
@@ -910,13 +925,14 @@ class CosyVoice2Model:
             live = [(p, t) for p, t, err in zip(batch, toks, errs) if err is None]
             utts = [dict(token=torch.tensor(t, dtype=torch.int32).unsqueeze(0), prompt_token=p.fpt, prompt_feat=p.feat, embedding=p.femb)
                     for p, t in live]
+            skw = self._solver_kw([p.uuid for p, _ in live])                   # (mixed step counts: inference_batch runs one call per count)
             try:
-                mels = self.flow.inference_batch(utts, streaming=False, finalize=True) if utts else []
+                mels = self.flow.inference_batch(utts, streaming=False, finalize=True, **skw) if utts else []
             except Exception:                                                  # e.g. one utterance beyond the flow's length limit
                 mels = []
                 for (p, _), u in zip(live, utts):
                     try:
-                        mels.append(self.flow.inference_batch([u], streaming=False, finalize=True)[0])
+                        mels.append(self.flow.inference_batch([u], streaming=False, finalize=True, **self._solver_kw([p.uuid]))[0])
                     except Exception as e:
                         p.exc = e
                         mels.append(None)
@@ -1232,6 +1248,7 @@ class CosyVoice2Model:
                 self.stretch_dict.pop(this_uuid, None)
                 self.out_dict.pop(this_uuid, None)
                 self.samp_dict.pop(this_uuid, None)
+                self.solver_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
 
@@ -1241,7 +1258,7 @@ class CosyVoice2Model:
             llm_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             flow_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             prompt_speech_feat=torch.zeros(1, 0, 80), source_speech_token=torch.zeros(1, 0, dtype=torch.int32), stream=False, speed=1.0,
-            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, sampling=None, **kwargs):
+            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, sampling=None, solver=None, **kwargs):
         """force_len (an extension; the reference swallows unknown keywords in **kwargs): synthetic-weights mode of SURVEY.md §8(d) —
         exactly that many speech tokens, EOS and fill ids never drawn — so that benchmark work is deterministic without a checkpoint.
         device_output (an extension, non-streaming coalesced calls only): 'tts_speech' stays on the model's device instead of the reference's
@@ -1251,7 +1268,10 @@ class CosyVoice2Model:
         of the whole call.  A non-final chunk may then be empty.  The defaults take exactly the path without them.
         sampling (an extension, every mode): a cv2amd.sampling.Sampling -- the call's own sampler settings (temperature, top_p, top_k, win_size,
         tau_r, greedy) and seed.  A seeded call's LLM draws and vocoder noise are functions of (seed, segment, step, trial) / (seed, segment,
-        chunk) alone, whatever slot, batch or round serves it.  None, or nothing set: the model's sampler and counter seed."""
+        chunk) alone, whatever slot, batch or round serves it.  None, or nothing set: the model's sampler and counter seed.
+        solver (an extension, every mode): a cv2amd.solver.Solver -- the call's own flow solver settings: Euler steps (1 .. 31) and guidance
+        rate (>= 0).  Calls with different rates share flow launches, calls with different step counts run in launches of their own
+        (DESIGN.md section 1).  None, or nothing set: the model's (cosyvoice2.yaml) on exactly the path without it."""
         from collections.abc import Generator
         vc = source_speech_token.shape[1] != 0                   # vc_job (model.py:141-143): the tokens are given, no LLM
         bistream = isinstance(text, Generator)                    # llm_job's bistream branch (model.py:120-128)
@@ -1263,6 +1283,8 @@ class CosyVoice2Model:
             O.check_rate(output_sample_rate)   # one of cv2amd.outrate.RATES: refused before any work
         if sampling is not None:
             sampling = None if sampling.is_default() else sampling.check()      # out-of-range settings: refused before any work
+        if solver is not None:
+            solver = None if solver.is_default() else solver.check()
         out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
         this_uuid = str(uuid.uuid1())
         # the current device is per thread and a new thread starts on device 0: callers run tts() from pool threads (the evaluation
@@ -1283,6 +1305,8 @@ class CosyVoice2Model:
                 self.out_dict[this_uuid] = self._Out(out_rate, pcm16, self.device)
             if sampling is not None:
                 self.samp_dict[this_uuid] = [sampling, 0]
+            if solver is not None:
+                self.solver_dict[this_uuid] = solver
         if bistream and not vc:
             with self._bi_cv:                                                 # the hub waits (briefly) for calls on their way in before its first feed
                 self._bi_incoming += 1
@@ -1318,6 +1342,7 @@ class CosyVoice2Model:
                     self.stretch_dict.pop(this_uuid, None)
                     self.out_dict.pop(this_uuid, None)
                     self.samp_dict.pop(this_uuid, None)
+                    self.solver_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
             return
@@ -1338,6 +1363,7 @@ class CosyVoice2Model:
                 if self.flow_cache and self.prompt_cache_max > 0:              # identity of the prompt: tokens + checksums of mel and embedding
                     pkey = (tuple(flow_prompt_speech_token.flatten().tolist()), float(prompt_speech_feat.double().sum()),
                             float(flow_embedding.double().sum()))
+                    pkey = pkey + SV.resolve(solver, self.flow)                # (a prompt's cache belongs to the t grid and guidance rate it was run under)
                 with self.lock:
                     self._first_pending[this_uuid] = t_call
                     self._first_need[slot] = hop + prompt_token_pad + la        # (model.py:353-357: what the first chunk waits for)
@@ -1403,5 +1429,6 @@ class CosyVoice2Model:
                 self.stretch_dict.pop(this_uuid, None)
                 self.out_dict.pop(this_uuid, None)
                 self.samp_dict.pop(this_uuid, None)
+                self.solver_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)

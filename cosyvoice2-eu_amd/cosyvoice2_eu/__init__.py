@@ -27,6 +27,10 @@ class Cosy2EU:
         return Cosy2EU(self._model.sampler(seed=seed, temperature=temperature, top_p=top_p, top_k=top_k, win_size=win_size, tau_r=tau_r,
                                            greedy=greedy))
 
+    def solver(self, steps=None, cfg_rate=None) -> 'Cosy2EU':
+        """A view of this object (same model) whose calls run the flow with their own Euler steps / guidance rate: CosyVoice2.solver."""
+        return Cosy2EU(self._model.solver(steps=steps, cfg_rate=cfg_rate))
+
     def tts(self, text: str, prompt: str, *, speed: float = 1.0, text_frontend: bool = False) -> Tuple[torch.Tensor, int]:
         prompt_16k = load_wav(prompt, 16000)
         segments = [out['tts_speech'] for out in self._model.inference_cross_lingual(text, prompt_16k, stream=False, speed=speed,

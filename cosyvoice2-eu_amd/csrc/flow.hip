@@ -20,9 +20,12 @@
 #include "gemm_launch.h"
 #include "skinny_launch.h"
 #include "../../include/cv2_amd.h"
+#include "flow_tspan.h"
 #include <algorithm>
 #include <map>
 #include <math.h>
+#include <cmath>
+#include <string.h>
 #include <atomic>
 #include <vector>
 
@@ -219,6 +222,7 @@ struct PackArgs {
     // utterance (noise, prompt mel) and its mu row is mu_start[s] + pos0[s] + t.  twin = row distance to the uncond twin; rows
     // below `lead` belong to no sequence (their twin rows do not exist).
     const int* pos0; const int* mu_start; int twin, lead;
+    const float* cfg_seq;        // [U] guidance rate of every utterance (a call with its own solver settings); null: `cfg` for all
 };
 template <class OP>
 __global__ __launch_bounds__(256) void k_euler_pack(PackArgs a) {
@@ -238,7 +242,8 @@ __global__ __launch_bounds__(256) void k_euler_pack(PackArgs a) {
                 x = *reinterpret_cast<const f32x4*>(a.x + (size_t)row * 80 + c);
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.v + (size_t)row * 80 + c);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.v + (size_t)(row + a.twin) * 80 + c);
-                x = x + a.dt * ((1.0f + a.cfg) * v0 - a.cfg * v1);
+                const float cfg = a.cfg_seq ? a.cfg_seq[s] : a.cfg;
+                x = x + a.dt * ((1.0f + cfg) * v0 - cfg * v1);
             }
             const size_t mrow = a.mu_start ? (size_t)((long)a.mu_start[s] + pt) : (size_t)row;      // (mu_start may be negative: first mu row minus the cached frames)
             mu = *reinterpret_cast<const f32x4*>(a.mu + mrow * 80 + c);
@@ -897,6 +902,11 @@ struct cv2_flow {
     float* t_steps_dev;          // [n_timesteps]
     float* tmp_t;                // [32][1024] x 3 scratch for the time MLP
     std::vector<float> t_host, dt_host;
+    // schedules of calls with a step count of their own (cv2_flow_inference_ex): the table of n steps is rows [n (n - 1) / 2, + n) of
+    // temb_ex, built at the first call that asks for n and resident from then on (bit n of sched_mask); n == d.n_timesteps is temb_tab
+    float* temb_ex;              // [496][14][256]
+    std::vector<float> dt_ex[32];
+    uint32_t sched_mask = 0;
     // row buffers
     uint16_t *a0, *hb, *xa, *xbuf, *cat, *lnb, *qk, *vt, *att;           // bf16
     float *xf, *rf, *vf, *xs, *mu, *spk, *tmpf;                           // fp32
@@ -948,6 +958,7 @@ static size_t flow_carve(const cv2_flow_dims& d, cv2_flow* h, char* base) {
     f.e_ff = c.take<uint16_t>(RG * 2048); f.e_x = c.take<float>(R * 512); f.e_tmp = c.take<float>(R * 512);
     f.itab = c.take<int>((size_t)8 * itab_per(R, d.max_seqs));      // layouts 0-3, ints 4; cached streaming: layouts 5-6, ints 7
     f.ptab = c.take<void*>((size_t)8 * d.max_seqs + 64);
+    f.temb_ex = c.take<float>((size_t)496 * 14 * 256);              // behind everything else: the addresses of a default call stay
     return c.off;
 }
 
@@ -1036,6 +1047,58 @@ static int time_tables(cv2_flow* h, const float* t_dev, int n, float* tab_out, h
     return 0;
 }
 
+// t schedule of n Euler steps exactly as solve_euler walks it (flow_matching.py:91-121) over t_span = 1 - cos(linspace(0,1,n+1) * pi/2) in fp32,
+// torch's values (flow_tspan.h; at n = 10 they are what cosf gave here before): t[i] = the time the estimator sees at step i, dt[i] = the
+// step's width.  Host arithmetic only.
+extern "C" int cv2_flow_schedule(int32_t n, float* t_out, float* dt_out) {
+    CV2_CHECK(n >= 1 && n <= 31 && t_out && dt_out, "cv2_flow_schedule: n_timesteps %d outside 1 .. 31", n);
+    const float* span = kFlowTspan + kFlowTspanOff(n);
+    float t = span[0], dt = span[1] - span[0];
+    for (int st = 1; st <= n; st++) {
+        t_out[st - 1] = t; dt_out[st - 1] = dt;
+        t = t + dt;
+        if (st < n) dt = span[st + 1] - t;
+    }
+    return 0;
+}
+// time table and step widths of a call with n Euler steps: the engine's own, or one built here at its first use
+static int flow_sched(cv2_flow* h, int n, hipStream_t s, const float** tab, const float** dt) {
+    if (n == h->d.n_timesteps) { *tab = h->temb_tab; *dt = h->dt_host.data(); return 0; }
+    CV2_CHECK(n >= 1 && n <= 31, "flow: n_timesteps %d outside 1 .. 31", n);
+    float* ex = h->temb_ex + (size_t)(n * (n - 1) / 2) * 14 * 256;
+    if (!(h->sched_mask >> n & 1)) {
+        std::vector<float> t(n);
+        h->dt_ex[n].resize(n);
+        if (cv2_flow_schedule(n, t.data(), h->dt_ex[n].data())) return -1;
+        CV2_HIP(hipMemcpyAsync(h->t_steps_dev, t.data(), n * sizeof(float), hipMemcpyHostToDevice, s));
+        CV2_HIP(hipStreamSynchronize(s));            // host vector goes out of scope
+        if (time_tables(h, h->t_steps_dev, n, ex, s)) return -1;
+        CV2_HIP(hipStreamSynchronize(s));
+        h->sched_mask |= 1u << n;
+    }
+    *tab = ex; *dt = h->dt_ex[n].data();
+    return 0;
+}
+// the solver records of a call -> its step count and, when any utterance's guidance rate differs from the engine's, the rates of all
+// (cfg stays empty otherwise: the launches then take the engine's scalar, as a call without records does)
+static int flow_solver(const cv2_flow* h, const cv2_flow_solver* sv, int U, const char* who, int* n_out, std::vector<float>* cfg) {
+    *n_out = h->d.n_timesteps; cfg->clear();
+    if (!sv) return 0;
+    int first = -1; bool own = false;
+    std::vector<float> r(U);
+    for (int u = 0; u < U; u++) {
+        CV2_CHECK(sv[u].n_timesteps <= 31, "%s: utterance %d: n_timesteps %d outside 1 .. 31", who, u, sv[u].n_timesteps);
+        CV2_CHECK(std::isfinite(sv[u].cfg_rate), "%s: utterance %d: cfg_rate is not finite", who, u);
+        const int n = sv[u].n_timesteps <= 0 ? h->d.n_timesteps : sv[u].n_timesteps;
+        if (first < 0) { first = u; *n_out = n; }
+        CV2_CHECK(n == *n_out, "%s: utterances %d and %d ask for different step counts (%d and %d): one step count per call", who, first, u, *n_out, n);
+        r[u] = sv[u].cfg_rate < 0.f ? h->d.cfg_rate : sv[u].cfg_rate;
+        own |= memcmp(&r[u], &h->d.cfg_rate, sizeof(float)) != 0;
+    }
+    if (own) *cfg = r;
+    return 0;
+}
+
 extern "C" int cv2_flow_create(const cv2_flow_dims* d, const cv2_flow_weights* w, void* ws, size_t ws_bytes, void* stream, cv2_flow** out) {
     CV2_CHECK(d && w && ws && out, "cv2_flow_create: null argument");
     CV2_CHECK(d->max_rows % 128 == 0 && d->max_rows >= 256, "cv2_flow_create: max_rows must be a multiple of 128");
@@ -1047,22 +1110,9 @@ extern "C" int cv2_flow_create(const cv2_flow_dims* d, const cv2_flow_weights* w
     flow_carve(*d, h, (char*)ws);
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(ws, 0, cv2_flow_workspace_bytes(d), s) != hipSuccess) { delete h; return cv2_fail("cv2_flow_create: memset failed"); }
-    // t schedule exactly as solve_euler walks it (flow_matching.py:91-121): t_span = 1 - cos(linspace(0,1,n+1) * pi/2) in fp32
     const int n = d->n_timesteps;
-    std::vector<float> span(n + 1);
-    for (int i = 0; i <= n; i++) {
-        // torch.linspace (fp32): start + i*step for the first half, end - (n-i)*step for the second
-        const float step = 1.0f / (float)n;
-        const float lin = i < (n + 1) / 2 ? 0.0f + step * (float)i : 1.0f - step * (float)(n - i);
-        span[i] = 1.0f - cosf(lin * 0.5f * 3.14159265358979323846f);
-    }
     h->t_host.resize(n); h->dt_host.resize(n);
-    float t = span[0], dt = span[1] - span[0];
-    for (int st = 1; st <= n; st++) {
-        h->t_host[st - 1] = t; h->dt_host[st - 1] = dt;
-        t = t + dt;
-        if (st < n) dt = span[st + 1] - t;
-    }
+    cv2_flow_schedule(n, h->t_host.data(), h->dt_host.data());
     if (hipMemcpyAsync(h->t_steps_dev, h->t_host.data(), n * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) { delete h; return cv2_fail("cv2_flow_create: upload failed"); }
     if (time_tables(h, h->t_steps_dev, n, h->temb_tab, s)) { delete h; return -1; }
@@ -1078,12 +1128,13 @@ extern "C" int cv2_flow_destroy(cv2_flow* h) {
 // ------------------------------------------------------------------ estimator core
 struct EstCtx { cv2_flow* h; const Layout* L; const float* temb; int chunk; hipStream_t s;
                 const IncTabs* inc = nullptr; int step = 0, conv_i = 0, tb_i = 0;         // cached streaming: tables, Euler step, site counters
-                bool qkv_chained = false; };                                              // the next transformer block's q / k / v^T are already there (k_tail_rows2<true>)
+                bool qkv_chained = false;                                                 // the next transformer block's q / k / v^T are already there (k_tail_rows2<true>)
+                int nst = 0; };                                                           // cached streaming: Euler steps of the call (the tails' layout)
 
 // cached streaming: hand the conv at this site its left context and keep this call's last two input rows
 static int est_conv_tail(EstCtx& c, uint16_t* buf, int C) {
     if (!c.inc) return 0;
-    const int nst = c.h->d.n_timesteps, ci = c.conv_i++;
+    const int nst = c.nst, ci = c.conv_i++;
     CV2_CHECK(ci < INC_CONVS, "flow: conv site counter overflow");
     ConvTailArgs a{buf, C, c.L->tab(), *c.inc, (0 * nst + c.step) * INC_CONVS + ci, (1 * nst + c.step) * INC_CONVS + ci};
     hipLaunchKernelGGL(k_conv_tail, dim3(c.L->S), dim3(256), 0, c.s, a);
@@ -1554,10 +1605,12 @@ static int cv2_flow_encoder_t(cv2_flow* h, const float* xs, int32_t T, const flo
 }
 
 template <class OP>
-static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U, int32_t streaming, int32_t finalize, void* stream) {
+static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_solver* solver, int32_t U, int32_t streaming, int32_t finalize, void* stream) {
     CV2_CHECK(h && utts && U >= 1, "cv2_flow_inference: bad argument");
     CV2_CHECK(2 * U <= h->d.max_seqs, "cv2_flow_inference: %d utterances exceed max_seqs/2", U);
     hipStream_t s = (hipStream_t)stream;
+    int nst; std::vector<float> cfgs;
+    if (flow_solver(h, solver, U, "cv2_flow_inference", &nst, &cfgs)) return -1;
     const int la = finalize ? 0 : 3;                      // pre_lookahead_len (flow.py:260-263)
     std::vector<int> lensT, lens2, lensE;
     for (int u = 0; u < U; u++) {
@@ -1573,6 +1626,8 @@ static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U
     Layout LE = make_layout(lensE);
     if (check_rows(h, LE, "cv2_flow_inference")) return -1;
     const int RU = L2.rows;
+    const float* temb_tab; const float* dts;
+    if (flow_sched(h, nst, s, &temb_tab, &dts)) return -1;
     if (upload_layout(h, LA, 0, s) || upload_layout(h, LT, 1, s) || upload_layout(h, L2, 2, s) || upload_layout(h, LE, 3, s)) return -1;
     // pointer / int tables
     {
@@ -1582,11 +1637,14 @@ static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U
             ptrs[u] = utts[u].embedding; ptrs[U + u] = utts[u].prompt_feat; ptrs[2 * U + u] = utts[u].mel_out; ptrs[3 * U + u] = utts[u].tokens;
             ints[u] = utts[u].n_prompt_feat;
         }
+        if (!cfgs.empty()) { ints.resize(2 * U); memcpy(&ints[U], cfgs.data(), U * sizeof(float)); }       // [n_prompt U][cfg_rate U]
+        CV2_CHECK(ints.size() <= itab_per(h->R, h->d.max_seqs), "cv2_flow_inference: int table overflow");
         CV2_HIP(hipMemcpyAsync(h->ptab, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice, s));
         int* ibase = h->itab + (size_t)4 * itab_per(h->R, h->d.max_seqs);
         CV2_HIP(hipMemcpyAsync(ibase, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, s));
         CV2_HIP(hipStreamSynchronize(s));
         const void* const* dp = (const void* const*)h->ptab;
+        const float* cfg_seq = cfgs.empty() ? nullptr : reinterpret_cast<const float*>(ibase + U);
         auto launches = [&](hipStream_t s) -> int {
         // speaker projection
         SpkArgs sp{(const float* const*)dp, h->w.spk_w, h->w.spk_b, h->spk};
@@ -1602,18 +1660,17 @@ static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U
         }
         // Euler loop (flow_matching.py:91-121)
         EstCtx c{h, &LE, nullptr, streaming ? 50 : 0, s};
-        for (int st = 0; st < h->d.n_timesteps; st++) {
+        for (int st = 0; st < nst; st++) {
             PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, st == 0 ? h->w.rand_noise : nullptr,
-                       st == 0 ? nullptr : h->vf, st == 0 ? 0.f : h->dt_host[st - 1], h->d.cfg_rate, L2.tab(), RU, U, GB(h->a0, 320),
-                       nullptr, nullptr, RU, 0};
+                       st == 0 ? nullptr : h->vf, st == 0 ? 0.f : dts[st - 1], h->d.cfg_rate, L2.tab(), RU, U, GB(h->a0, 320),
+                       nullptr, nullptr, RU, 0, cfg_seq};
             hipLaunchKernelGGL(k_euler_pack<OP>, dim3(((long)RU * 20 + 255) / 256), dim3(256), 0, s, p);
-            c.temb = h->temb_tab + (size_t)st * 14 * 256;
+            c.temb = temb_tab + (size_t)st * 14 * 256;
             if (estimator_core<OP>(c)) return -1;
         }
         {   // last update without a following pack: reuse k_euler_pack (a0 is scratch now)
-            const int st = h->d.n_timesteps;
-            PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, nullptr, h->vf, h->dt_host[st - 1], h->d.cfg_rate,
-                       L2.tab(), RU, U, GB(h->a0, 320), nullptr, nullptr, RU, 0};
+            PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, nullptr, h->vf, dts[nst - 1], h->d.cfg_rate,
+                       L2.tab(), RU, U, GB(h->a0, 320), nullptr, nullptr, RU, 0, cfg_seq};
             hipLaunchKernelGGL(k_euler_pack<OP>, dim3(((long)RU * 20 + 255) / 256), dim3(256), 0, s, p);
         }
         int maxn2 = 1;
@@ -1632,8 +1689,12 @@ static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U
         const int graph_dbg = g_flow_graph.load();
         const bool graph_on = graph_dbg < 0 ? graph_env : graph_dbg != 0;
         if (!graph_on) { if (launches(s)) return -1; CV2_LAUNCH_CHECK(); return 0; }
-        std::vector<int> key{U, streaming, finalize, g_att_dma.load()};
+        std::vector<int> key{U, streaming, finalize, g_att_dma.load(), nst, (int)cfgs.size()};
         for (int u = 0; u < U; u++) { key.push_back(utts[u].n_tok); key.push_back(utts[u].n_prompt_feat); }
+        // each utterance's cfg_rate bits: more than replay needs (the rates reach the kernels through the int table uploaded above, so the
+        // step count and cfgs.size() would do) -- a server whose clients send arbitrary rates captures a graph per distinct set of them
+        // and ages useful shapes out of the FG_MAX entries; the replay is off by default
+        for (float r : cfgs) { int b; memcpy(&b, &r, sizeof b); key.push_back(b); }                 // each utterance's cfg_rate bits
         auto it = h->graphs.find(key);
         if (it == h->graphs.end()) {
             int& n = h->seen[key];
@@ -1678,14 +1739,17 @@ static int cv2_flow_inference_t(cv2_flow* h, const cv2_flow_utt* utts, int32_t U
 }
 
 // ------------------------------------------------------------------ cached streaming
-static size_t inc_kv_elems(const cv2_flow* h, long frames) { return (size_t)2 * h->d.n_timesteps * INC_TBLOCKS * frames * 1024; }
-static size_t inc_tail_elems(const cv2_flow* h) { return (size_t)2 * 2 * h->d.n_timesteps * INC_CONVS * 1024; }
+// (nst = the Euler steps of the stream's calls: slots [branch][nst][56], tails [branch][generation][nst][31])
+static size_t inc_kv_elems(int nst, long frames) { return (size_t)2 * nst * INC_TBLOCKS * frames * 1024; }
+static size_t inc_tail_elems(int nst) { return (size_t)2 * 2 * nst * INC_CONVS * 1024; }
 
-static size_t enc_part_off(const cv2_flow* h, long frames) { return inc_kv_elems(h, frames) + inc_tail_elems(h); }     // elements in front of the encoder part
-extern "C" size_t cv2_flow_cache_bytes(const cv2_flow* h, int32_t frames) {
-    if (!h || frames < 64 || frames % 64) return 0;
-    return (enc_part_off(h, frames) + enc_elems(frames)) * sizeof(uint16_t);
+static size_t enc_part_off(int nst, long frames) { return inc_kv_elems(nst, frames) + inc_tail_elems(nst); }     // elements in front of the encoder part
+extern "C" size_t cv2_flow_cache_bytes_ex(const cv2_flow* h, int32_t frames, int32_t n_timesteps) {
+    if (!h || frames < 64 || frames % 64 || n_timesteps > 31) return 0;
+    const int nst = n_timesteps <= 0 ? h->d.n_timesteps : n_timesteps;
+    return (enc_part_off(nst, frames) + enc_elems(frames)) * sizeof(uint16_t);
 }
+extern "C" size_t cv2_flow_cache_bytes(const cv2_flow* h, int32_t frames) { return cv2_flow_cache_bytes_ex(h, frames, 0); }
 
 // first n frames of every slot (and the convolution tails) of one cache -> another cache of a different capacity: a stream that
 // starts from a prompt another call has already run (same prompt tokens, prompt mel, speaker embedding) begins with that prefix
@@ -1708,22 +1772,24 @@ __global__ __launch_bounds__(256) void k_cache_copy(CacheCopyArgs a) {      // g
         }
     }
 }
-extern "C" int cv2_flow_cache_copy(const cv2_flow* h, const void* src, int32_t src_frames, void* dst, int32_t dst_frames, int32_t n_frames,
-                                   void* stream) {
+extern "C" int cv2_flow_cache_copy_ex(const cv2_flow* h, const void* src, int32_t src_frames, void* dst, int32_t dst_frames, int32_t n_frames,
+                                      int32_t n_timesteps, void* stream) {
     CV2_CHECK(h && src && dst && src != dst, "cv2_flow_cache_copy: bad argument");
+    CV2_CHECK(n_timesteps <= 31, "cv2_flow_cache_copy: n_timesteps %d outside 1 .. 31", n_timesteps);
+    const int nst = n_timesteps <= 0 ? h->d.n_timesteps : n_timesteps;
     CV2_CHECK(src_frames >= 64 && src_frames % 64 == 0 && dst_frames >= 64 && dst_frames % 64 == 0, "cv2_flow_cache_copy: capacities must be multiples of 64");
     CV2_CHECK(n_frames >= 0 && n_frames % 50 == 0 && n_frames <= src_frames && n_frames <= dst_frames, "cv2_flow_cache_copy: %d frames (whole chunks of 50, within both capacities)", n_frames);
     hipStream_t s = (hipStream_t)stream;
-    const int slots = 2 * h->d.n_timesteps * INC_TBLOCKS;
+    const int slots = 2 * nst * INC_TBLOCKS;
     if (n_frames > 0) {
         CacheCopyArgs a{(const uint16_t*)src, (uint16_t*)dst, (long)src_frames, (long)dst_frames, (int)n_frames};
         hipLaunchKernelGGL(k_cache_copy, dim3(slots, 16), dim3(256), 0, s, a);
     }
-    CV2_HIP(hipMemcpyAsync((uint16_t*)dst + inc_kv_elems(h, dst_frames), (const uint16_t*)src + inc_kv_elems(h, src_frames),
-                           inc_tail_elems(h) * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+    CV2_HIP(hipMemcpyAsync((uint16_t*)dst + inc_kv_elems(nst, dst_frames), (const uint16_t*)src + inc_kv_elems(nst, src_frames),
+                           inc_tail_elems(nst) * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
     {   // the encoder part: keys / values of the first n_frames / 2 tokens (layers 0-5) and n_frames frames (layers 6-9), the conv tails
-        const uint16_t* se = (const uint16_t*)src + enc_part_off(h, src_frames);
-        uint16_t* de = (uint16_t*)dst + enc_part_off(h, dst_frames);
+        const uint16_t* se = (const uint16_t*)src + enc_part_off(nst, src_frames);
+        uint16_t* de = (uint16_t*)dst + enc_part_off(nst, dst_frames);
         for (int l = 0; l < ENC_LAYERS && n_frames > 0; l++) {
             const int n = l < 6 ? n_frames / 2 : n_frames;
             EncCacheCopyArgs a{se + enc_layer_off(src_frames, l), de + enc_layer_off(dst_frames, l), l < 6 ? enc_capT(src_frames) : enc_capE(src_frames),
@@ -1735,13 +1801,19 @@ extern "C" int cv2_flow_cache_copy(const cv2_flow* h, const void* src, int32_t s
     CV2_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int cv2_flow_cache_copy(const cv2_flow* h, const void* src, int32_t src_frames, void* dst, int32_t dst_frames, int32_t n_frames,
+                                   void* stream) {
+    return cv2_flow_cache_copy_ex(h, src, src_frames, dst, dst_frames, n_frames, 0, stream);
+}
 
 template <class OP>
-static int cv2_flow_inference_chunk_t(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, int32_t U, int32_t finalize,
-                                        void* stream) {
+static int cv2_flow_inference_chunk_t(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, const cv2_flow_solver* solver, int32_t U,
+                                        int32_t finalize, void* stream) {
     CV2_CHECK(h && utts && refs && U >= 1, "cv2_flow_inference_chunk: bad argument");
     CV2_CHECK(2 * U <= h->d.max_seqs, "cv2_flow_inference_chunk: %d utterances exceed max_seqs/2", U);
     hipStream_t s = (hipStream_t)stream;
+    int nst; std::vector<float> cfgs;
+    if (flow_solver(h, solver, U, "cv2_flow_inference_chunk", &nst, &cfgs)) return -1;
     const int la = finalize ? 0 : 3;
     std::vector<int> lensT, lens2, lensN, lensNE;
     for (int u = 0; u < U; u++) {
@@ -1767,22 +1839,26 @@ static int cv2_flow_inference_chunk_t(cv2_flow* h, const cv2_flow_utt* utts, con
     Layout LIE = make_layout(lensNE, INC_LEAD);
     if (check_rows(h, L2, "cv2_flow_inference_chunk") || check_rows(h, LIE, "cv2_flow_inference_chunk")) return -1;
     const int RI = LI.rows, twin = RI - INC_LEAD;
+    const float* temb_tab; const float* dts;
+    if (flow_sched(h, nst, s, &temb_tab, &dts)) return -1;
     if (upload_layout(h, LA, 0, s) || upload_layout(h, LT, 1, s) || upload_layout(h, L2, 2, s) || upload_layout(h, LI, 5, s) ||
         upload_layout(h, LIE, 6, s)) return -1;
     const size_t per = itab_per(h->R, h->d.max_seqs);
     CV2_CHECK((size_t)12 * U + 16 <= per, "cv2_flow_inference_chunk: int table overflow");
     // pointer tables: [emb U][prompt U][mel_out U][tokens U][kv 2U][tails 2U]; int tables: [n_prompt U][skip U][mu_start U][pos0 2U][frames 2U][gen 2U]
+    // and, for a call whose utterances bring guidance rates of their own, [cfg_rate U]
     std::vector<const void*> ptrs(8 * U);
     std::vector<int> ints(9 * U);
+    if (!cfgs.empty()) { ints.resize(10 * U); memcpy(&ints[9 * U], cfgs.data(), U * sizeof(float)); }
     int maxn2 = 1;
     for (int u = 0; u < U; u++) {
         ptrs[u] = utts[u].embedding; ptrs[U + u] = utts[u].prompt_feat; ptrs[2 * U + u] = utts[u].mel_out;
         ptrs[3 * U + u] = utts[u].tokens + (enc_cache ? refs[u].n_cached / 2 : 0);       // (the embedding kernel starts at the first new token)
         const long fr = refs[u].cache_frames;
         uint16_t* base = (uint16_t*)refs[u].cache;
-        uint16_t* tails = base + inc_kv_elems(h, fr);
-        ptrs[4 * U + u] = base; ptrs[5 * U + u] = base + inc_kv_elems(h, fr) / 2;
-        ptrs[6 * U + u] = tails; ptrs[7 * U + u] = tails + inc_tail_elems(h) / 2;
+        uint16_t* tails = base + inc_kv_elems(nst, fr);
+        ptrs[4 * U + u] = base; ptrs[5 * U + u] = base + inc_kv_elems(nst, fr) / 2;
+        ptrs[6 * U + u] = tails; ptrs[7 * U + u] = tails + inc_tail_elems(nst) / 2;
         const int nc = refs[u].n_cached, skip = std::max(utts[u].n_prompt_feat - nc, 0);
         ints[u] = utts[u].n_prompt_feat; ints[U + u] = skip; ints[2 * U + u] = enc_cache ? L2.start[u] - nc : L2.start[u];      // mu row of frame pt: this + pt
         ints[3 * U + u] = ints[4 * U + u] = nc;
@@ -1804,7 +1880,7 @@ static int cv2_flow_inference_chunk_t(cv2_flow* h, const cv2_flow_utt* utts, con
     hipLaunchKernelGGL(k_embed_tokens_ptr<OP>, dim3((LA.rows + 1) / 2), dim3(256), 0, s, ea);
     EncInc einc;
     for (int u = 0; enc_cache && u < U; u++) {
-        einc.base.push_back((uint16_t*)refs[u].cache + enc_part_off(h, refs[u].cache_frames));
+        einc.base.push_back((uint16_t*)refs[u].cache + enc_part_off(nst, refs[u].cache_frames));
         einc.frames.push_back(refs[u].cache_frames); einc.n0_tok.push_back(refs[u].n_cached / 2); einc.gen.push_back(refs[u].gen);
     }
     if (encoder_core<OP>(h, LA, LT, L2, 1, nullptr, s, enc_cache ? &einc : nullptr)) return -1;
@@ -1815,14 +1891,15 @@ static int cv2_flow_inference_chunk_t(cv2_flow* h, const cv2_flow_utt* utts, con
     }
     // Euler loop over the new frames only
     EstCtx c{h, &LIE, nullptr, 50, s};
-    c.inc = &tabs;
-    for (int st = 0; st <= h->d.n_timesteps; st++) {
+    c.inc = &tabs; c.nst = nst;
+    const float* cfg_seq = cfgs.empty() ? nullptr : reinterpret_cast<const float*>(ibase + 9 * U);
+    for (int st = 0; st <= nst; st++) {
         PackArgs p{h->xs, h->mu, h->spk, (const float* const*)(dp + U), ibase, st == 0 ? h->w.rand_noise : nullptr,
-                   st == 0 ? nullptr : h->vf, st == 0 ? 0.f : h->dt_host[st - 1], h->d.cfg_rate, LI.tab(), RI, U, GB(h->a0, 320),
-                   ibase + 3 * U, ibase + 2 * U, twin, INC_LEAD};
+                   st == 0 ? nullptr : h->vf, st == 0 ? 0.f : dts[st - 1], h->d.cfg_rate, LI.tab(), RI, U, GB(h->a0, 320),
+                   ibase + 3 * U, ibase + 2 * U, twin, INC_LEAD, cfg_seq};
         hipLaunchKernelGGL(k_euler_pack<OP>, dim3(((long)RI * 20 + 255) / 256), dim3(256), 0, s, p);
-        if (st == h->d.n_timesteps) break;                       // last update: no estimator call follows
-        c.temb = h->temb_tab + (size_t)st * 14 * 256;
+        if (st == nst) break;                                    // last update: no estimator call follows
+        c.temb = temb_tab + (size_t)st * 14 * 256;
         c.step = st;
         if (estimator_core<OP>(c)) return -1;
     }
@@ -1843,12 +1920,20 @@ extern "C" int cv2_flow_estimator(cv2_flow* h, float* x, const float* mask, cons
 extern "C" int cv2_flow_encoder(cv2_flow* h, const float* xs, int32_t T, const float* context, int32_t streaming, float* out, void* stream) {
     return FLOW_OPS(cv2_flow_encoder_t, h, xs, T, context, streaming, out, stream);
 }
+extern "C" int cv2_flow_inference_ex(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_solver* solver, int32_t U, int32_t streaming,
+                                     int32_t finalize, void* stream) {
+    return FLOW_OPS(cv2_flow_inference_t, h, utts, solver, U, streaming, finalize, stream);
+}
 extern "C" int cv2_flow_inference(cv2_flow* h, const cv2_flow_utt* utts, int32_t U, int32_t streaming, int32_t finalize, void* stream) {
-    return FLOW_OPS(cv2_flow_inference_t, h, utts, U, streaming, finalize, stream);
+    return cv2_flow_inference_ex(h, utts, nullptr, U, streaming, finalize, stream);
+}
+extern "C" int cv2_flow_inference_chunk_ex(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, const cv2_flow_solver* solver,
+                                           int32_t U, int32_t finalize, void* stream) {
+    return FLOW_OPS(cv2_flow_inference_chunk_t, h, utts, refs, solver, U, finalize, stream);
 }
 extern "C" int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, int32_t U, int32_t finalize,
                                         void* stream) {
-    return FLOW_OPS(cv2_flow_inference_chunk_t, h, utts, refs, U, finalize, stream);
+    return cv2_flow_inference_chunk_ex(h, utts, refs, nullptr, U, finalize, stream);
 }
 #undef FLOW_OPS
 

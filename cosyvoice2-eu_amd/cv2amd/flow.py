@@ -10,6 +10,7 @@ import ctypes as C
 import torch
 
 from . import lib as L
+from . import solver as SV
 from . import weights as W
 
 
@@ -63,13 +64,23 @@ class FlowCacheRef(C.Structure):
     _fields_ = [('cache', C.c_void_p), ('cache_frames', C.c_int32), ('n_cached', C.c_int32), ('gen', C.c_int32)]
 
 
-class FlowCache:
-    """Per-stream state of cv2_flow_inference_chunk: the device buffer (zero-initialised) plus what the next call needs to know."""
-    __slots__ = ('buf', 'frames', 'n_cached', 'gen')
+class FlowSolver(C.Structure):
+    _fields_ = [('n_timesteps', C.c_int32), ('cfg_rate', C.c_float)]
 
-    def __init__(self, engine, max_frames):
+
+class FlowCache:
+    """Per-stream state of cv2_flow_inference_chunk: the device buffer (zero-initialised) plus what the next call needs to know.
+    `pair` = the resolved (steps, cfg_rate) the stream runs under: the layout depends on the step count, and the keys / values it holds
+    were made on that t grid under that guidance rate."""
+    __slots__ = ('buf', 'frames', 'n_cached', 'gen', 'pair')
+
+    def __init__(self, engine, max_frames, solver=None):
+        self.pair = engine._pairs(solver, 1)[0]
         self.frames = (int(max_frames) + 63) // 64 * 64
-        nbytes = engine.lib.cv2_flow_cache_bytes(engine.handle, self.frames)
+        if self.pair == engine.pair:
+            nbytes = engine.lib.cv2_flow_cache_bytes(engine.handle, self.frames)
+        else:
+            nbytes = engine.lib.cv2_flow_cache_bytes_ex(engine.handle, self.frames, self.pair[0])
         if nbytes == 0:
             raise ValueError(f'flow cache: bad capacity {self.frames}')
         self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=engine.device)
@@ -89,6 +100,13 @@ def _bind(lib):
     lib.cv2_flow_cache_bytes.argtypes = [C.c_void_p, C.c_int32]
     lib.cv2_flow_cache_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.cv2_flow_inference_chunk.argtypes = [C.c_void_p, C.POINTER(FlowUtt), C.POINTER(FlowCacheRef), C.c_int32, C.c_int32, C.c_void_p]
+    lib.cv2_flow_inference_ex.argtypes = [C.c_void_p, C.POINTER(FlowUtt), C.POINTER(FlowSolver), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.cv2_flow_inference_chunk_ex.argtypes = [C.c_void_p, C.POINTER(FlowUtt), C.POINTER(FlowCacheRef), C.POINTER(FlowSolver), C.c_int32, C.c_int32,
+                                                C.c_void_p]
+    lib.cv2_flow_cache_bytes_ex.restype = C.c_size_t
+    lib.cv2_flow_cache_bytes_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.cv2_flow_cache_copy_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.cv2_flow_schedule.argtypes = [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.cv2_flow_estimator.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p]
     lib.cv2_flow_encoder.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.cv2_gemm_bf16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
@@ -204,6 +222,8 @@ class FlowEngine:
         self.dims = FlowDims(max_rows=2 * max_utts * per, max_seqs=2 * max_utts, max_len=max_len, n_timesteps=n_timesteps,
                              cfg_rate=cfg_rate, operands=OPERANDS[operands])
         self.max_utts, self.max_len = max_utts, max_len
+        self.n_timesteps, self.cfg_rate = int(n_timesteps), float(cfg_rate)
+        self.pair = SV.Solver().resolve(self)                        # what a call without solver settings runs under
         nbytes = self.lib.cv2_flow_workspace_bytes(C.byref(self.dims))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         h = C.c_void_p()
@@ -219,10 +239,29 @@ class FlowEngine:
             pass
 
     # ---- CausalMaskedDiffWithXvec.inference (flow.py:235-283), batched ---------------------------------------
-    def inference_batch(self, utts, streaming=False, finalize=True):
+    def _pairs(self, solver, n):
+        """solver: None, one cv2amd.solver.Solver for all, or a list with one (or None) per utterance -> the resolved (steps, cfg_rate) of
+        each of the n utterances.  ValueError for a value out of range or a list of another length, before any work."""
+        if solver is None or isinstance(solver, SV.Solver):
+            solver = [solver] * n
+        if len(solver) != n:
+            raise ValueError(f'solver: {len(solver)} settings for {n} utterances')
+        return [(s or SV.Solver()).check().resolve(self) for s in solver]
+
+    @staticmethod
+    def _records(pairs):
+        arr = (FlowSolver * len(pairs))()
+        for i, (n, rate) in enumerate(pairs):
+            arr[i] = FlowSolver(n, rate)
+        return arr
+
+    def inference_batch(self, utts, streaming=False, finalize=True, solver=None):
         """utts: list of dicts token [1,n] int, prompt_token [1,P] int, prompt_feat [1,F,80], embedding [1,192].
-        Returns a list of mel tensors [1, 80, T2] (device, fp32)."""
+        solver: the call's cv2amd.solver.Solver, or a list with one per utterance (None: the engine's steps and guidance rate).  Utterances
+        with different guidance rates share a launch; different step counts run as one entry-point call per step count, each in the
+        caller's order.  Returns a list of mel tensors [1, 80, T2] (device, fp32) in the caller's order."""
         assert 1 <= len(utts) <= self.max_utts
+        pairs = self._pairs(solver, len(utts))
         dev = self.device
         arr = (FlowUtt * len(utts))()
         outs, keep = [], []
@@ -237,40 +276,62 @@ class FlowEngine:
             keep += [tok, pf, emb]
             outs.append(out)
             arr[i] = FlowUtt(tok.data_ptr(), tok.numel(), pf.data_ptr(), pf.shape[0], emb.data_ptr(), out.data_ptr())
-        L.check(self.lib.cv2_flow_inference(self.handle, arr, len(utts), int(streaming), int(finalize), L.stream_ptr()))
+        if all(p == self.pair for p in pairs):                       # nothing set: the call without records
+            L.check(self.lib.cv2_flow_inference(self.handle, arr, len(utts), int(streaming), int(finalize), L.stream_ptr()))
+        else:
+            for n in sorted({p[0] for p in pairs}):                  # one entry-point call per step count
+                idx = [i for i, p in enumerate(pairs) if p[0] == n]
+                sub = (FlowUtt * len(idx))(*[arr[i] for i in idx])
+                L.check(self.lib.cv2_flow_inference_ex(self.handle, sub, self._records([pairs[i] for i in idx]), len(idx), int(streaming),
+                                                       int(finalize), L.stream_ptr()))
         self._last_keep = keep
         return outs
 
     # ---- the same call for streams that keep a cache: only the frames after the cached ones are computed and returned --------
-    def new_cache(self, max_frames):
-        return FlowCache(self, max_frames)
+    def new_cache(self, max_frames, solver=None):
+        return FlowCache(self, max_frames, solver)
 
-    def clone_cache(self, src, max_frames):
-        """A new cache of capacity >= max_frames that starts with everything `src` holds (a prompt another call has already run)."""
-        dst = FlowCache(self, max(max_frames, src.n_cached))
-        L.check(self.lib.cv2_flow_cache_copy(self.handle, src.buf.data_ptr(), src.frames, dst.buf.data_ptr(), dst.frames, src.n_cached,
-                                             L.stream_ptr()))
+    def clone_cache(self, src, max_frames, solver=None):
+        """A new cache of capacity >= max_frames that starts with everything `src` holds (a prompt another call has already run).  It runs
+        under src's solver settings; `solver`, when given, must resolve to them (ValueError: keys / values made on another t grid or under
+        another guidance rate would be silently wrong)."""
+        if solver is not None and self._pairs(solver, 1)[0] != src.pair:
+            raise ValueError(f'flow cache: made under (steps, cfg_rate) = {src.pair}, asked for {self._pairs(solver, 1)[0]}')
+        dst = FlowCache(self, max(max_frames, src.n_cached), SV.Solver(*src.pair))
+        if src.pair == self.pair:
+            L.check(self.lib.cv2_flow_cache_copy(self.handle, src.buf.data_ptr(), src.frames, dst.buf.data_ptr(), dst.frames, src.n_cached,
+                                                 L.stream_ptr()))
+        else:
+            L.check(self.lib.cv2_flow_cache_copy_ex(self.handle, src.buf.data_ptr(), src.frames, dst.buf.data_ptr(), dst.frames, src.n_cached,
+                                                    src.pair[0], L.stream_ptr()))
         dst.n_cached, dst.gen = src.n_cached, src.gen
         return dst
 
-    def prompt_cache(self, prompt_token, prompt_feat, embedding, hop=25):
+    def prompt_cache(self, prompt_token, prompt_feat, embedding, hop=25, solver=None):
         """The cache of a prompt alone: the whole chunks of the prompt whose look-ahead lies inside the prompt (flow.py:260-263 needs
         pre_lookahead_len tokens after the last one).  None when the prompt is shorter than one chunk plus the look-ahead."""
         P = int(prompt_token.numel())
         n_full = (P - self.pre_lookahead_len) // hop * hop
         if n_full <= 0:
             return None
-        c = FlowCache(self, self.token_mel_ratio * n_full)
+        c = FlowCache(self, self.token_mel_ratio * n_full, solver)
         u = dict(token=prompt_token.reshape(1, -1)[:, :0], prompt_token=prompt_token.reshape(1, -1)[:, :n_full + self.pre_lookahead_len],
                  prompt_feat=prompt_feat.reshape(1, -1, 80)[:, :self.token_mel_ratio * n_full], embedding=embedding)
-        self.inference_chunk_batch([u], [c], finalize=False)
+        self.inference_chunk_batch([u], [c], finalize=False, solver=solver)
         return c
 
-    def inference_chunk_batch(self, utts, caches, finalize):
+    def inference_chunk_batch(self, utts, caches, finalize, solver=None):
         """utts as for inference_batch (token = the whole prefix so far), caches[i] = the stream's FlowCache.  Returns
         [(mel [1, 80, n] fp32, first) ...]: the frames from index `first` of the mel the recompute would return (flow.py:281).
-        The caches advance only when the whole call succeeded."""
+        The caches advance only when the whole call succeeded.  solver as for inference_batch; every stream's setting must resolve to
+        the pair its cache was created for, and all streams of one call to one step count (ValueError otherwise: the caller groups)."""
         assert 1 <= len(utts) <= self.max_utts and len(caches) == len(utts)
+        pairs = self._pairs(solver, len(utts))
+        for i, (p, c) in enumerate(zip(pairs, caches)):
+            if p != c.pair:
+                raise ValueError(f'flow cache: utterance {i} runs under (steps, cfg_rate) = {p}, its cache was made under {c.pair}')
+        if len({p[0] for p in pairs}) > 1:
+            raise ValueError(f'flow cache: one call has one step count, got {sorted({p[0] for p in pairs})}')
         dev = self.device
         arr, refs = (FlowUtt * len(utts))(), (FlowCacheRef * len(utts))()
         outs, keep, ends = [], [], []
@@ -290,17 +351,20 @@ class FlowEngine:
             ends.append(t2)
             arr[i] = FlowUtt(tok.data_ptr(), tok.numel(), pf.data_ptr(), pf.shape[0], emb.data_ptr(), out.data_ptr())
             refs[i] = FlowCacheRef(c.buf.data_ptr(), c.frames, c.n_cached, c.gen)
-        L.check(self.lib.cv2_flow_inference_chunk(self.handle, arr, refs, len(utts), int(finalize), L.stream_ptr()))
+        if all(p == self.pair for p in pairs):
+            L.check(self.lib.cv2_flow_inference_chunk(self.handle, arr, refs, len(utts), int(finalize), L.stream_ptr()))
+        else:
+            L.check(self.lib.cv2_flow_inference_chunk_ex(self.handle, arr, refs, self._records(pairs), len(utts), int(finalize), L.stream_ptr()))
         for c, t2 in zip(caches, ends):
             c.n_cached, c.gen = t2, c.gen + 1
         self._last_keep = keep
         return outs
 
     def inference(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding, streaming,
-                  finalize):
+                  finalize, solver=None):
         assert token.shape[0] == 1                                            # flow.py:246
         mel = self.inference_batch([dict(token=token, prompt_token=prompt_token, prompt_feat=prompt_feat, embedding=embedding)],
-                                   streaming, finalize)[0]
+                                   streaming, finalize, solver=solver)[0]
         return mel, None
 
     # ---- inner seams, exposed for parity tests -----------------------------------------------------------------

@@ -331,6 +331,30 @@ int cv2_flow_inference_chunk(cv2_flow* h, const cv2_flow_utt* utts, const cv2_fl
  * same `gen` as the source.  The source must hold exactly n_frames (its tails belong to that position). */
 int cv2_flow_cache_copy(const cv2_flow* h, const void* src, int32_t src_frames, void* dst, int32_t dst_frames, int32_t n_frames, void* stream);
 
+/* Solver settings of a call (an extension: the reference passes n_timesteps to CausalConditionalCFM.forward and reads inference_cfg_rate
+ * inside solve_euler, flow_matching.py:71-123; cv2_flow_dims fixes both per engine).  One record per utterance:
+ *   n_timesteps   Euler steps 1 .. 31 on the cosine grid t_span = 1 - cos(linspace(0, 1, n + 1) * pi / 2); <= 0: the engine's
+ *   cfg_rate      classifier-free-guidance rate, finite and >= 0 (at 0 both branches still run); < 0: the engine's
+ * The update of a step is x + dt * ((1 + cfg_rate) * v_cond - cfg_rate * v_uncond) with the utterance's own rate, so utterances with
+ * different rates share a launch.  ALL records of one call must resolve to the same step count (the estimator's time embedding and the
+ * number of launches are the call's); a call that mixes them, or carries a value out of range, returns -1 before any launch.  The time
+ * table of a step count other than the engine's is built at its first use and stays resident in the workspace.  solver == NULL is
+ * cv2_flow_inference / cv2_flow_inference_chunk: the same launches with the same arguments.
+ * A stream's cache is laid out for its step count (slots [n][56], convolution tails [2][n][31]) and holds keys / values made on that t
+ * grid under that guidance rate: size it with cv2_flow_cache_bytes_ex, copy it with cv2_flow_cache_copy_ex and keep one (n_timesteps,
+ * cfg_rate) for all calls of a stream -- the entry points cannot tell what a cache was filled with.  n_timesteps <= 0 there: the engine's.
+ * cv2_flow_schedule writes the t and dt of the n steps as the Euler loops walk them (host arithmetic, no device needed).
+ * Adding these entry points changed no struct and no signature: CV2_ABI_VERSION stays. */
+typedef struct { int32_t n_timesteps; float cfg_rate; } cv2_flow_solver;
+int cv2_flow_inference_ex(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_solver* solver, int32_t n_utts, int32_t streaming,
+                          int32_t finalize, void* stream);
+int cv2_flow_inference_chunk_ex(cv2_flow* h, const cv2_flow_utt* utts, const cv2_flow_cache_ref* refs, const cv2_flow_solver* solver,
+                                int32_t n_utts, int32_t finalize, void* stream);
+size_t cv2_flow_cache_bytes_ex(const cv2_flow* h, int32_t cache_frames, int32_t n_timesteps);
+int cv2_flow_cache_copy_ex(const cv2_flow* h, const void* src, int32_t src_frames, void* dst, int32_t dst_frames, int32_t n_frames,
+                           int32_t n_timesteps, void* stream);
+int cv2_flow_schedule(int32_t n_timesteps, float* t_out, float* dt_out);
+
 /* Test hook: 1 or -1 = the default forms of the estimator attention (key / value tiles by LDS DMA: one key group from 512 blocks of
  * 8 heads x 64 query rows on -- 257 for a full-context call without cache --, four key groups below), 0 = the reference: one
  * register-staged kernel with one key group at every size.  The DMA forms permute a tile's keys among the score rows (the same products
