@@ -22,7 +22,8 @@ What is different, by design:
         batch and HiFT on the pool's HIP streams;
       - NON-STREAMING calls are COALESCED: each call queues its request, one caller becomes the batch leader, waits `coalesce_ms`
         for stragglers, and runs up to `max_batch` queued requests as one batch through the three stages (one decode step serves
-        all of them, the flow runs over the packed ragged batch, HiFT on a pool of streams);
+        all of them, the flow runs over the packed ragged batch, HiFT on a pool of streams); a JOINED call (tts_joined) queues all
+        segments of its text at once, so one caller fills a batch, and joins their waveforms on the device (DESIGN.md section 1);
       - the two kinds exclude each other (a batch uses slots 0..n-1): streams hold the model in shared mode, a batch in exclusive mode.
 """
 import logging
@@ -971,16 +972,15 @@ class CosyVoice2Model:
             for p in batch:
                 p.done.set()
 
-    def _tts_coalesced(self, p):
-        with self.lock:
-            self._pending.append(p)
-        while not p.done.is_set():
+    def _coalesce_wait(self, ps):
+        """Leader election of the queued non-streaming callers, until every one of this caller's requests `ps` is done."""
+        while not all(p.done.is_set() for p in ps):
             # another caller is the leader: block on its lock (it is released right after the batch's results are set).  Polling
             # here (31 waiting callers waking every 0.5 ms) fought the leader's Python for the GIL: 20-70 ms per batch of 32
             if not self._leader_lock.acquire(timeout=0.05):
                 continue
             try:
-                if p.done.is_set():
+                if all(p.done.is_set() for p in ps):
                     break
                 self._enter_excl()                                             # streams drain first; new ones wait for the batch
                 try:
@@ -998,9 +998,113 @@ class CosyVoice2Model:
                     self._exit_excl()
             finally:
                 self._leader_lock.release()
+
+    def _tts_coalesced(self, p):
+        with self.lock:
+            self._pending.append(p)
+        self._coalesce_wait([p])
         if p.exc is not None:
             raise p.exc
         return p.speech
+
+    def _drop_call(self, this_uuid):
+        """the per-uuid state of a call that has ended (model.py:395-398)"""
+        with self.lock:
+            if self._token_log is not None:
+                self._token_log[this_uuid] = list(self.tts_speech_token_dict.get(this_uuid, []))
+            self.tts_speech_token_dict.pop(this_uuid, None)
+            self.llm_end_dict.pop(this_uuid, None)
+            self.hift_cache_dict.pop(this_uuid, None)
+            self.stretch_dict.pop(this_uuid, None)
+            self.out_dict.pop(this_uuid, None)
+            self.samp_dict.pop(this_uuid, None)
+            self.solver_dict.pop(this_uuid, None)
+        self._hift_pin.pop(this_uuid, None)
+        self._flow_caches.pop(this_uuid, None)
+
+    def tts_joined(self, inputs, join, speed=1.0, force_len=None, device_output=False, output_sample_rate=None, pcm16=False, sampling=None,
+                   solver=None):
+        """A joined call (an extension, non-streaming only): the text segments of ONE call -- `inputs`, the list of
+        per-segment keyword dicts tts() takes -- queued together, so that they run as one coalesced batch (several when there are more than
+        `max_batch`; other callers' requests may share them), their 24 kHz waveforms joined on the device under `join` (a cv2amd.join.Join:
+        pause, optional trim of interior silences with a fade) and converted / copied to the host ONCE.  A generator that yields one dict:
+        {'tts_speech': [1, n], 'segments': [(start, end), ...]}, start / end of every segment in the joined 24 kHz signal (before the output
+        conversion).  sampling: one Sampling or a list aligned with the segments; force_len: an int or a list.  If a segment fails, the first
+        failure in segment order is raised and nothing is yielded.  The test hooks of single calls (_noise_hook, _trace) are not consulted."""
+        from cv2amd import join as J
+        inputs = list(inputs)
+        k = len(inputs)
+        if join is None or join.is_default():
+            raise ValueError('tts_joined: no join settings (a call without them is tts())')
+        join.check()                                                          # out-of-range settings: refused before any work
+        if not 1 <= k <= J.MAX_PIECES:
+            raise ValueError(f'tts_joined: {k} segments, 1 .. {J.MAX_PIECES} can be joined')
+        for kw in inputs:
+            if not isinstance(kw.get('text'), torch.Tensor) or ('source_speech_token' in kw and kw['source_speech_token'].shape[1] != 0):
+                raise TypeError('tts_joined: every segment needs a tensor of token ids as its text (no generator text, no voice conversion)')
+        if output_sample_rate is not None:
+            O.check_rate(output_sample_rate)
+        samplings = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * k
+        force_lens = list(force_len) if isinstance(force_len, (list, tuple)) else [force_len] * k
+        if len(samplings) != k or len(force_lens) != k:
+            raise ValueError('tts_joined: sampling / force_len lists must have one entry per segment')
+        samplings = [None if s is None or s.is_default() else s.check() for s in samplings]
+        if solver is not None:
+            solver = None if solver.is_default() else solver.check()
+        out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
+        torch.cuda.set_device(self.device)
+        dev, ps = self.device, []
+        empty_i = torch.zeros(1, 0, dtype=torch.int32)
+        try:
+            for kw, sp, fl in zip(inputs, samplings, force_lens):
+                this_uuid = str(uuid.uuid1())
+                if self._on_call is not None:
+                    self._on_call(this_uuid)
+                p = self._Pending()
+                p.uuid, p.done, p.speech, p.exc = this_uuid, threading.Event(), None, None
+                ps.append(p)
+                with self.lock:
+                    self.tts_speech_token_dict[this_uuid], self.llm_end_dict[this_uuid] = [], False
+                    self.hift_cache_dict[this_uuid] = None
+                    if sp is not None:
+                        self.samp_dict[this_uuid] = [sp, 0]
+                    if solver is not None:
+                        self.solver_dict[this_uuid] = solver
+                p.text, p.prompt_text = kw['text'].to(dev), kw.get('prompt_text', empty_i).to(dev)
+                p.llm_ptok = kw.get('llm_prompt_speech_token', empty_i).to(dev)
+                p.fpt = kw.get('flow_prompt_speech_token', empty_i).to(dev)
+                p.feat = kw.get('prompt_speech_feat', torch.zeros(1, 0, 80)).to(dev)
+                p.femb = kw.get('flow_embedding', torch.zeros(0, 192)).to(dev)
+                p.speed, p.force_len, p.sampling = speed, fl, sp
+                p.dev_out, p.out = True, None                                  # the waveform stays on the device; converted once, after the join
+            with self.lock:                                                   # adjacent and in order
+                self._pending.extend(ps)
+            self._coalesce_wait(ps)
+            for p in ps:
+                if p.exc is not None:
+                    raise p.exc
+            wavs = [p.speech for p in ps]
+            pause, F, g = join.resolve()
+            with self.run_lock:
+                bounds = None
+                if g is not None:
+                    bounds = J.wave_bounds(wavs, g)[0].cpu().tolist()          # the one copy of 2 k integers
+                pieces, N, spans = J.plan([w.shape[1] for w in wavs], bounds, join)
+                speech = J.wave_join(wavs, pieces, N, F).unsqueeze(0)
+                if pcm16 or out_rate != O.MODEL_RATE:
+                    speech = self._out_convert([(self._Out(out_rate, pcm16, dev), speech, True)])[0]
+                if device_output:
+                    torch.cuda.current_stream().synchronize()
+                else:
+                    speech = speech.cpu()
+            yield {'tts_speech': speech, 'segments': spans}
+        finally:
+            with self.lock:                                                   # (an abandoned or refused call: nothing of it stays queued)
+                for p in ps:
+                    if p in self._pending:
+                        self._pending.remove(p)
+            for p in ps:
+                self._drop_call(p.uuid)
 
     # ---- llm_job's bistream branch (model.py:120-128) for ALL generator-text calls: one round loop -------------------------------
     class _BiCall:
@@ -1333,18 +1437,7 @@ class CosyVoice2Model:
             try:
                 yield {'tts_speech': self._tts_coalesced(p)}
             finally:
-                with self.lock:
-                    if self._token_log is not None:
-                        self._token_log[this_uuid] = list(self.tts_speech_token_dict.get(this_uuid, []))
-                    self.tts_speech_token_dict.pop(this_uuid, None)
-                    self.llm_end_dict.pop(this_uuid, None)
-                    self.hift_cache_dict.pop(this_uuid, None)
-                    self.stretch_dict.pop(this_uuid, None)
-                    self.out_dict.pop(this_uuid, None)
-                    self.samp_dict.pop(this_uuid, None)
-                    self.solver_dict.pop(this_uuid, None)
-                self._hift_pin.pop(this_uuid, None)
-                self._flow_caches.pop(this_uuid, None)
+                self._drop_call(this_uuid)
             return
         t_call = time.perf_counter()
         slot = self._enter_shared()

@@ -504,6 +504,42 @@ int cv2_out_resample(const cv2_out_args* a, void* stream);                      
  * memory, uploaded by the caller ahead of this call on `stream`. */
 int cv2_out_resample_batch(const cv2_out_args* args, const cv2_out_args* table_dev, int32_t n, void* stream);
 
+/* Joined calls (an extension: the reference yields the segments of a split text one by one, cli/cosyvoice.py:181-210): the 24 kHz waveforms
+ * s_0 .. s_{k-1} (lengths n_i, fp32 device, aligned to 4 bytes only) of ONE call's text segments written into one waveform on the device.
+ *
+ * cv2_wave_bounds -- the kept range [a_i, b_i) of every segment when interior silences are trimmed, all k segments in one call:
+ *   frames of 240 samples without overlap, frame f = [240 f, min(240 f + 240, n_i));  peak_f = max |s_i[q]| over the frame, a NaN sample
+ *   counting as 0;  P_i = max_f peak_f;  thr_i = P_i * g, ONE fp32 product (g = float32(10 ** (-trim_db / 20)), rounded once on the host);
+ *   frame f is loud iff P_i > 0 and peak_f >= thr_i.  With f_lo / f_hi the first / last loud frame and keep = 480:
+ *       a_i = max(0, 240 f_lo - keep) for i > 0, else 0;      b_i = min(n_i, 240 (f_hi + 1) + keep) for i < k - 1, else n_i;
+ *   a segment with P_i == 0 keeps a_i = 0, b_i = n_i.  Only interior edges are trimmed.  Every quantity is a maximum or the one rounded
+ *   product: integer atomics (atomicMin / atomicMax, order-independent; P_i through the bit pattern of a non-negative float) and no float
+ *   atomic, so a host restatement gives the same integers.  bounds_dev [k][2] receives (a_i, b_i), peaks_dev [k] receives P_i; both are
+ *   written whole (no need to clear them).  Three stream operations (a clear of peaks_dev, the peaks, the loud frames), one entry-point call.
+ * cv2_wave_join -- the pieces s_i[src_off .. src_off + m) written to dst[dst_off .. dst_off + m), pieces in ascending dst_off, one launch:
+ *   with CV2_WAVE_FADE_IN the first F samples of a piece are multiplied by w[t], with CV2_WAVE_FADE_OUT its last F samples by w[F - 1 - t]
+ *   (t counted from the start of the faded range; w = fade_table_dev [F], 0.5 - 0.5 cos(pi (t + 0.5) / F) in fp64 rounded once to fp32 on
+ *   the host): ONE fp32 multiply per sample; every other sample of a piece is copied bit for bit; every sample of dst[0 .. n_dst) that no
+ *   piece covers is written as +0.0f (dst need not be cleared).  dst is aligned to 4 bytes only.
+ * Both take their records twice, as cv2_out_resample_batch does: on the host (checked here: k in 1 .. CV2_WAVE_MAX_PIECES; segment
+ * lengths n in 1 .. 2^30 for the bounds, 0 <= m <= n_src <= 2^30 for a piece -- an empty piece writes nothing --; 0 < g <= 1; pieces
+ * ordered, not overlapping, inside n_dst and inside their sources; F >= 0; a fade flag needs m >= 2 F; -1 and cv2_last_error otherwise,
+ * nothing launched) and in device memory, uploaded by the caller ahead of the call on `stream`.
+ * Adding these entry points changed no struct and no signature: CV2_ABI_VERSION stays. */
+#define CV2_WAVE_MAX_PIECES 256
+#define CV2_WAVE_FADE_IN 1
+#define CV2_WAVE_FADE_OUT 2
+typedef struct {
+    const float* src; int32_t n; int32_t reserved;
+} cv2_wave_seg;                                                      /* 16 bytes */
+typedef struct {
+    const float* src; int32_t n_src, src_off, m, dst_off, fade, reserved;
+} cv2_wave_piece;                                                    /* 32 bytes */
+int cv2_wave_bounds(const cv2_wave_seg* segs, const cv2_wave_seg* segs_dev, int32_t k, float g, int32_t* bounds_dev, float* peaks_dev,
+                    void* stream);
+int cv2_wave_join(const cv2_wave_piece* pieces, const cv2_wave_piece* pieces_dev, int32_t k, const float* fade_table_dev, int32_t F,
+                  float* dst, int32_t n_dst, void* stream);
+
 /* =====================================================================================================================
  * Prompt features (the extractor that feeds this path): replaces the reference's
  *   feat_extractor = matcha.utils.audio.mel_spectrogram(n_fft 1920, num_mels 80, sampling_rate 24000, hop_size 480, win_size 1920,
