@@ -17,6 +17,7 @@ from cosyvoice.cli.model import CosyVoice2Model
 class CosyVoice2:
     flow_solver = None              # a .solver(...) view's cv2amd.solver.Solver; None: the model's flow steps and guidance rate
     join = None                     # a .joined(...) view's cv2amd.join.Join; None: the segments of a split text are yielded one by one
+    stream_join = None              # a .continuous(...) view's cv2amd.join.Join; None: the segments of a split text stream as separate calls
 
     def __init__(self, model_dir, load_jit=False, load_trt=False, load_vllm=False, fp16=False, trt_concurrent=1, setting='original',
                  llm_run_id=None, flow_run_id=None, hifigan_run_id=None, final=False, backbone=None, frontend=None, state_dicts=None,
@@ -164,6 +165,33 @@ class CosyVoice2:
         new.check()
         view = copy.copy(self)
         view.join = None if new.is_default() else new
+        if view.join is not None:
+            view.stream_join = None                                         # (one view is joined or continuous: the later request holds)
+        return view
+
+    def continuous(self, pause_ms=None, trim_db=None, fade_ms=None):
+        """A view of this object (same model, same frontend) whose STREAMING calls run the segments of a split text as ONE stream: one
+        generator and one 24 kHz signal -- piece 0, the pause, piece 1, ... -- through ONE output record, so the resampler does not restart
+        at the seams; the next segment's LLM runs ahead while the previous one's last chunks are vocoded.  Yields {'tts_speech': chunk,
+        'segment': i}, the last chunk also 'segments': [(start, end), ...] (positions in the 24 kHz signal); a chunk may be empty.
+        pause_ms = silence between segments, 0 .. 5000 (150 when another field is set); trim_db = gate away the silence at interior
+        segment edges down to 20 ms around the loud frames, 20 .. 80 (None: keep everything); fade_ms = raised-cosine fade at gated edges,
+        0 .. 5 (5 with trim_db; refused without it).  The gate is causal -- a frame is loud when within trim_db of the loudest frame SO FAR
+        in the call -- and deliberately not the trim of .joined(), whose threshold needs the segment's peak and so the segment's end; the
+        same text may be cut at other samples by the two.  None keeps this object's setting; with nothing set anywhere the view is the
+        plain object.  Anything out of range raises ValueError here, before the model is touched; stream=False on a continuous view raises
+        ValueError (use .joined() for one waveform).  A generator text or a text of one segment takes the plain streaming path.  speed
+        applies per segment.  Composes with .output(), .sampler() and .solver()."""
+        import copy
+        from cv2amd.join import Join, check_continuous
+        new = Join(pause_ms=pause_ms, trim_db=trim_db, fade_ms=fade_ms)
+        if self.stream_join is not None:
+            new = self.stream_join.replace(pause_ms=new.pause_ms, trim_db=new.trim_db, fade_ms=new.fade_ms)
+        check_continuous(new)
+        view = copy.copy(self)
+        view.stream_join = None if new.is_default() else new
+        if view.stream_join is not None:
+            view.join = None
         return view
 
     def list_available_spks(self):
@@ -197,12 +225,21 @@ class CosyVoice2:
             start_time = time.time()
 
     def _segments(self, tts_text, stream, text_frontend):
-        """-> (the text's segments, whether they run as ONE joined call).  A joined view refuses stream=True before any work; a generator
-        text or a text of one segment takes the plain path."""
+        """-> (the text's segments, whether they run as ONE joined or continuous call).  A joined view refuses stream=True and a continuous
+        view stream=False before any work; a generator text or a text of one segment takes the plain path."""
         if self.join is not None and stream:
             raise ValueError('a joined view yields one waveform per call: stream=True is not supported on it')
+        if self.stream_join is not None and not stream:
+            raise ValueError('a continuous view streams its call: stream=False is not supported on it (.joined() yields one waveform)')
         texts = self.frontend.text_normalize(tts_text, split=True, text_frontend=text_frontend)
-        return texts, self.join is not None and len(texts) > 1 and all(isinstance(t, str) for t in texts)
+        one = self.join is not None or self.stream_join is not None
+        return texts, one and len(texts) > 1 and all(isinstance(t, str) for t in texts)
+
+    def _run_as_one(self, model_inputs, speed, label):
+        """the segments as ONE call: continuous (streaming; _segments has seen stream=True) on a continuous view, else joined"""
+        if self.stream_join is not None:
+            return self._run_continuous(model_inputs, speed, label)
+        return self._run_joined(model_inputs, speed, label)
 
     def _run_joined(self, model_inputs, speed, label):
         start_time = time.time()
@@ -219,12 +256,28 @@ class CosyVoice2:
             logging.info('yield speech len {}, rtf {}'.format(speech_len, (time.time() - start_time) / speech_len))
             yield model_output
 
+    def _run_continuous(self, model_inputs, speed, label):
+        start_time = time.time()
+        logging.info('synthesis text {} ({} segments, continuous)'.format(label, len(model_inputs)))
+        extra = {}
+        if self.output_sample_rate is not None or self.output_pcm16:
+            extra = dict(output_sample_rate=self.output_sample_rate, pcm16=self.output_pcm16)
+        if self.sampling is not None:                                       # (segment k: stream k under the one seed, as on the plain path)
+            extra['sampling'] = [self.sampling.for_segment(i) for i in range(len(model_inputs))]
+        if self.flow_solver is not None:
+            extra['solver'] = self.flow_solver
+        for model_output in self.model.tts_continuous(model_inputs, self.stream_join, speed=speed, **extra):
+            speech_len = model_output['tts_speech'].shape[1] / self.sample_rate
+            logging.info('yield speech len {}, rtf {}'.format(speech_len, (time.time() - start_time) / max(speech_len, 1e-9)))
+            yield model_output
+            start_time = time.time()
+
     def inference_sft(self, tts_text, spk_id, stream=False, speed=1.0, text_frontend=True):
         """cli/cosyvoice.py:81-90 (inherited by CosyVoice2): a speaker of spk2info by id, no prompt.  A CosyVoice2 model dir has no
         spk2info.pt, so an unknown `spk_id` raises the reference's KeyError (frontend.py:487)."""
         texts, joined = self._segments(tts_text, stream, text_frontend)
         if joined:
-            yield from self._run_joined([self.frontend.frontend_sft(i, spk_id) for i in texts], speed, tts_text)
+            yield from self._run_as_one([self.frontend.frontend_sft(i, spk_id) for i in texts], speed, tts_text)
             return
         for seg, i in enumerate(texts):
             model_input = self.frontend.frontend_sft(i, spk_id)
@@ -237,7 +290,7 @@ class CosyVoice2:
             for i in texts:
                 if len(i) < 0.5 * len(prompt_text):
                     logging.warning('synthesis text {} too short than prompt text {}, this may lead to bad performance'.format(i, prompt_text))
-            yield from self._run_joined([self.frontend.frontend_zero_shot(i, prompt_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
+            yield from self._run_as_one([self.frontend.frontend_zero_shot(i, prompt_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
                                          for i in texts], speed, tts_text)
             return
         for seg, i in enumerate(texts):
@@ -249,7 +302,7 @@ class CosyVoice2:
     def inference_cross_lingual(self, tts_text, prompt_speech_16k, zero_shot_spk_id='', stream=False, speed=1.0, text_frontend=True):
         texts, joined = self._segments(tts_text, stream, text_frontend)
         if joined:
-            yield from self._run_joined([self.frontend.frontend_cross_lingual(i, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
+            yield from self._run_as_one([self.frontend.frontend_cross_lingual(i, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
                                          for i in texts], speed, tts_text)
             return
         for seg, i in enumerate(texts):
@@ -268,7 +321,7 @@ class CosyVoice2:
         """cli/cosyvoice.py:284-295: same three stages, the instruction rides in the prompt-text slot."""
         texts, joined = self._segments(tts_text, stream, text_frontend)
         if joined:
-            yield from self._run_joined([self.frontend.frontend_instruct2(i, instruct_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
+            yield from self._run_as_one([self.frontend.frontend_instruct2(i, instruct_text, prompt_speech_16k, self.model_sample_rate, zero_shot_spk_id)
                                          for i in texts], speed, tts_text)
             return
         for seg, i in enumerate(texts):

@@ -142,6 +142,7 @@ class CosyVoice2Model:
         self._prefill_lock = threading.Lock()  # one thread at a time drains _prefill_q (alone with newcomer_beside, inside run_lock without it)
         self._adv_lock = threading.Lock()      # _llm_advance's bookkeeping (it used to rely on run_lock alone)
         self._first_need = {}                  # slot -> tokens the call's first chunk needs, until that chunk is submitted
+        self._ahead = set()                    # slots of continuous calls' looked-ahead segments: in _first_need for their tokens, but not about to submit
         self._chunks_active = 0                # chunk rounds (flow + HiFT) in progress: decode bursts beside them take the launches
         self._bi_incoming = 0                  # generator-text calls that have entered tts() but not yet joined the hub
         self._sched_log = None                 # diagnostics (tools/bench_bistream.py): list receiving (t, kind, info) of hub / chunk rounds
@@ -155,6 +156,7 @@ class CosyVoice2Model:
         self.stretch_dict = {}                 # uuid -> _Stretcher of a streaming call with speed != 1; created and dropped with hift_cache_dict[uuid]
         self.out_dict = {}                     # uuid -> _Out of a call with output_sample_rate / pcm16; created and dropped with hift_cache_dict[uuid]
         self.samp_dict = {}                    # uuid -> [Sampling, vocoder invocations so far] of a call with its own sampler settings / seed; likewise
+        self.cont_dict = {}                    # call id -> cv2amd.join.WaveStream of a continuous call (tts_continuous): device state record and held samples
         self.solver_dict = {}                  # uuid -> cv2amd.solver.Solver of a call with its own flow steps / guidance rate; likewise
         self._hift_pin, self._pin_rr = {}, -1  # uuid -> index of the HiftPool engine / HIP stream serving that call's chunks
         self.llm_stream = torch.cuda.Stream(self.device)   # (torch.cuda.Stream.priority_range() is (0, -1) here: no priority below the default exists)
@@ -470,7 +472,7 @@ class CosyVoice2Model:
 
     # ---- chunks of concurrent streams: one ragged flow batch for every chunk that is ready -------------------------------
     class _Chunk:
-        __slots__ = ('token', 'fpt', 'feat', 'femb', 'offset', 'uuid', 'stream', 'finalize', 'done', 'speech', 'exc', 'cap_hint', 'pkey', 'taken', 'speed')
+        __slots__ = ('token', 'fpt', 'feat', 'femb', 'offset', 'uuid', 'stream', 'finalize', 'done', 'speech', 'exc', 'cap_hint', 'pkey', 'taken', 'speed', 'keep_dev')
 
     def _flow_cache_for(self, c):
         """The call's flow cache, large enough for this chunk.  Capacity: the caller's estimate of the utterance (frames), at least
@@ -569,7 +571,7 @@ class CosyVoice2Model:
                 if batched is not None:                                        # one vocoder call per chunk shape instead of one per chunk
                     for c, w in zip(grp, self._out_chunks(grp, batched)):
                         if w is not None:
-                            c.speech = w.cpu()
+                            c.speech = w if c.keep_dev else w.cpu()      # (a continuous call's chunk meets its seam on the device first)
                     continue
                 used = sorted({self._hift_pin.setdefault(c.uuid, self._next_pin()) for c in grp})
                 for k in used:
@@ -594,7 +596,7 @@ class CosyVoice2Model:
                         w.record_stream(main)
                 for c, w in zip(grp, self._out_chunks(grp, sp)):
                     if w is not None:
-                        c.speech = w.cpu()
+                        c.speech = w if c.keep_dev else w.cpu()
         except BaseException as e:                                            # not attributable to one chunk: every waiting stream sees it
             for c in batch:
                 if c.speech is None and c.exc is None:
@@ -610,12 +612,13 @@ class CosyVoice2Model:
         self._pin_rr = (self._pin_rr + 1) % len(self.hift_pool.engines)
         return self._pin_rr
 
-    def _chunk_submit(self, token, fpt, feat, femb, offset, this_uuid, stream, finalize, cap_hint=None, pkey=None, first_slot=None, speed=1.0):
+    def _chunk_submit(self, token, fpt, feat, femb, offset, this_uuid, stream, finalize, cap_hint=None, pkey=None, first_slot=None, speed=1.0, keep_dev=False):
         """token2wav for one chunk of a streaming call.  The chunk is queued; whoever gets the device next runs the flow over ALL
         queued chunks as one ragged batch (streams that share decode steps become ready together), then HiFT per chunk."""
         c = self._Chunk()
         c.token, c.fpt, c.feat, c.femb, c.offset, c.uuid, c.stream, c.finalize = token, fpt, feat, femb, offset, this_uuid, stream, finalize
         c.done, c.speech, c.exc, c.cap_hint, c.pkey, c.taken, c.speed = False, None, None, cap_hint, pkey, False, speed
+        c.keep_dev = keep_dev
         with self.lock:
             self._chunk_q.append(c)
         if self._sched_log is not None:
@@ -652,7 +655,7 @@ class CosyVoice2Model:
             waited = False
             while not c.done and not c.taken and time.perf_counter() < t_end:
                 with self.lock:
-                    near = any(self._enq.get(sl, 0) >= n for sl, n in self._first_need.items() if sl not in self._joining)
+                    near = any(self._enq.get(sl, 0) >= n for sl, n in self._first_need.items() if sl not in self._joining and sl not in self._ahead)
                     have_first = any(q.offset == 0 and q.stream and not q.finalize for q in self._chunk_q)
                 if not near or have_first:
                     break
@@ -707,10 +710,13 @@ class CosyVoice2Model:
         return c.speech
 
     # ---- llm side: llm_job (model.py:118-139) as bursts on the LLM stream -------------------------------------------
-    def _enter_shared(self, joining=True):
-        """A streaming / serial call takes one LLM slot; waits while a coalesced batch runs (or waits to run) or no slot is free."""
+    def _enter_shared(self, joining=True, wait=True):
+        """A streaming / serial call takes one LLM slot; waits while a coalesced batch runs (or waits to run) or no slot is free
+        (wait=False: returns None instead -- a continuous call's look-ahead takes a slot only when one is there)."""
         with self._mode:
             while self._excl or self._excl_waiting > 0 or not self._slot_free:
+                if not wait:
+                    return None
                 self._mode.wait(0.05)
             self._n_shared += 1
             slot = self._slot_free.pop(0)
@@ -1356,6 +1362,214 @@ class CosyVoice2Model:
                 self._hift_pin.pop(this_uuid, None)
                 self._flow_caches.pop(this_uuid, None)
 
+    # ---- the streaming loop of a tensor-text call (model.py:351-394), shared by tts() and the segments of tts_continuous() -----------
+    def _prompt_key(self, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, solver):
+        """identity of the prompt (host tensors): tokens + checksums of mel and embedding; None while prompt caches are off"""
+        if not (self.flow_cache and self.prompt_cache_max > 0):
+            return None
+        pkey = (tuple(flow_prompt_speech_token.flatten().tolist()), float(prompt_speech_feat.double().sum()), float(flow_embedding.double().sum()))
+        return pkey + SV.resolve(solver, self.flow)                            # (a prompt's cache belongs to the t grid and guidance rate it was run under)
+
+    def _stream_chunks(self, this_uuid, slot, text_d, ptext_d, lptok_d, fpt, feat, femb, pkey, force_len, sampling, speed, t_call,
+                       prefilled=False, on_llm_end=None, keep_dev=False):
+        """The chunks of one streaming call that owns `slot`: yields (speech, final).  prefilled: the slot's prefill has been enqueued
+        already (a continuous call's look-ahead); on_llm_end: called once, outside every lock, when the call's LLM is seen to have ended;
+        keep_dev: the chunks stay on the device."""
+        hop, la = self.token_hop_len, self.flow.pre_lookahead_len
+        token_offset = 0
+        prompt_token_pad = int(np.ceil(fpt.shape[1] / hop) * hop - fpt.shape[1])
+        # flow-cache capacity in frames: the forced length, else a typical 8 speech tokens per text token (grown when exceeded)
+        n_guess = force_len if force_len is not None else min(self._limits[2], 8 * int(text_d.shape[1]) + 64)
+        cap_hint = self.flow.token_mel_ratio * (fpt.shape[1] + n_guess)
+        if not prefilled:
+            with self.lock:
+                self._first_pending[this_uuid] = t_call
+                self._first_need[slot] = hop + prompt_token_pad + la            # (model.py:353-357: what the first chunk waits for)
+            self._llm_start(slot, text_d, ptext_d, lptok_d, force_len, sampling)     # prefill draws token 0; the first pass of the loop below
+        while True:                                                            # requests the rest of the first chunk's tokens
+            this_tok, finished = None, False
+            with self.run_lock:
+                this_token_hop_len = hop + prompt_token_pad if token_offset == 0 else hop
+                need = token_offset + this_token_hop_len + la
+                toks = self._llm_poll(this_uuid, slot, need)
+                ended = self.llm_end_dict[this_uuid]
+                if len(toks) >= need:
+                    if not ended:                                              # the next chunk's tokens beyond what is already enqueued (by this
+                        self._llm_advance(need + hop - max(len(toks), self._enq.get(slot, 0)), shared=True)    # or another stream): the burst
+                    this_tok = torch.tensor(toks[:need], dtype=torch.int32).unsqueeze(0)          # overlaps this chunk's flow + HiFT
+                elif ended:
+                    finished = True
+                else:
+                    self._llm_advance(need - len(toks))                        # nothing in flight any more (ids above EOS are steps without a token)
+            if ended and on_llm_end is not None:
+                on_llm_end()
+                on_llm_end = None
+            if this_tok is not None:
+                speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, True, False, cap_hint, pkey,
+                                            first_slot=slot if token_offset == 0 else None, speed=speed, keep_dev=keep_dev)
+                token_offset += this_token_hop_len
+                yield speech, False
+            if finished:
+                break
+        this_tok = torch.tensor(self.tts_speech_token_dict[this_uuid], dtype=torch.int32).unsqueeze(0)
+        yield self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True, speed=speed, keep_dev=keep_dev), True
+
+    def _close_stream_call(self, this_uuid, slot):
+        """the end of a call that owns a slot, finished or abandoned: the slot parked and freed, the per-uuid state dropped"""
+        with self.run_lock, self.llm_lock:                                    # an abandoned generator leaves a live slot behind: park it
+            with torch.cuda.stream(self.llm_stream):
+                self.llm.park(slot)
+            self.llm_stream.synchronize()
+        with self.lock:
+            self._first_pending.pop(this_uuid, None)
+            self._first_need.pop(slot, None)
+            self._ahead.discard(slot)
+        self._exit_shared(slot)
+        with self.lock:
+            if self._token_log is not None:
+                self._token_log[this_uuid] = list(self.tts_speech_token_dict.get(this_uuid, []))
+            self.tts_speech_token_dict.pop(this_uuid, None)
+            self.llm_end_dict.pop(this_uuid, None)
+            self.hift_cache_dict.pop(this_uuid, None)
+            self.stretch_dict.pop(this_uuid, None)
+            self.out_dict.pop(this_uuid, None)
+            self.samp_dict.pop(this_uuid, None)
+            self.solver_dict.pop(this_uuid, None)
+            self._hift_pin.pop(this_uuid, None)
+            self._flow_caches.pop(this_uuid, None)
+
+    # ---- continuous calls: the segments of one text as ONE stream ------------------------------------------------------------------
+    class _Seg:
+        __slots__ = ('uuid', 'slot', 'text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'pkey', 'force_len', 'sampling', 'prefilled', 'exc')
+
+    def _seg_open(self, kw, sampling, force_len, solver, speed, wait):
+        """One segment of a continuous call takes a slot and registers its per-uuid state, as a streaming tts() call does (no output
+        record: the call has ONE).  wait=False: None when no slot is free right now."""
+        slot = self._enter_shared(wait=wait)
+        if slot is None:
+            return None
+        sg = self._Seg()
+        sg.uuid, sg.slot, sg.force_len, sg.sampling, sg.prefilled, sg.exc = str(uuid.uuid1()), slot, force_len, sampling, False, None
+        try:
+            if self._on_call is not None:
+                self._on_call(sg.uuid)
+            with self.lock:
+                self.tts_speech_token_dict[sg.uuid], self.llm_end_dict[sg.uuid] = [], False
+                self.hift_cache_dict[sg.uuid] = None
+                if speed != 1.0:
+                    self.stretch_dict[sg.uuid] = self._Stretcher(speed)
+                if sampling is not None:
+                    self.samp_dict[sg.uuid] = [sampling, 0]
+                if solver is not None:
+                    self.solver_dict[sg.uuid] = solver
+            dev, empty_i = self.device, torch.zeros(1, 0, dtype=torch.int32)
+            fpt_h, feat_h = kw.get('flow_prompt_speech_token', empty_i), kw.get('prompt_speech_feat', torch.zeros(1, 0, 80))
+            femb_h = kw.get('flow_embedding', torch.zeros(0, 192))
+            sg.fpt, sg.feat, sg.femb = fpt_h.to(dev), feat_h.to(dev), femb_h.to(dev)
+            sg.text, sg.prompt_text = kw['text'].to(dev), kw.get('prompt_text', empty_i).to(dev)
+            sg.llm_ptok = kw.get('llm_prompt_speech_token', empty_i).to(dev)
+            sg.pkey = self._prompt_key(fpt_h, feat_h, femb_h, solver)
+        except BaseException:
+            self._close_stream_call(sg.uuid, slot)
+            raise
+        return sg
+
+    def _seg_ahead(self, sg):
+        """The look-ahead of a continuous call: the next segment's prefill goes on the LLM stream now, and its first chunk's tokens are
+        asked for in the shared bursts like any newcomer's (_first_need); the tokens wait in the slot until the segment's turn.  A failure
+        is kept for that turn."""
+        hop = self.token_hop_len
+        try:
+            with self.lock:
+                self._ahead.add(sg.slot)                                      # (no later chunk gives way to it: it submits at its turn only)
+                self._first_need[sg.slot] = int(np.ceil(sg.fpt.shape[1] / hop) * hop - sg.fpt.shape[1]) + hop + self.flow.pre_lookahead_len
+            self._llm_start(sg.slot, sg.text, sg.prompt_text, sg.llm_ptok, sg.force_len, sg.sampling)
+            sg.prefilled = True
+        except Exception as e:
+            sg.exc = e
+
+    def tts_continuous(self, inputs, join, speed=1.0, force_len=None, output_sample_rate=None, pcm16=False, sampling=None, solver=None):
+        """A continuous call (an extension, streaming only): the text segments of ONE call -- `inputs`, the list of
+        per-segment keyword dicts tts() takes -- streamed in order as one generator and ONE 24 kHz signal: piece 0, `pause` zeros, piece
+        1, ...; with trim_db the silences at interior edges are gated away and the gated edges fade (cv2amd.join.StreamPlan; the gate is
+        causal and is NOT the trim of tts_joined).  Every segment runs exactly the streaming path of tts() (its tokens and 24 kHz chunks
+        are the plain call's); when a segment's LLM has ended, the next one takes a slot, is prefilled and decodes in the shared bursts
+        while this one's last chunks run; flow and vocoder chunks run in segment order.  The call has ONE output record: the stream is the
+        conversion of the whole signal.  Yields {'tts_speech': chunk, 'segment': i}; the last chunk adds 'segments': [(start, end), ...],
+        the pieces' positions in the 24 kHz signal.  A chunk may be empty.  sampling: one Sampling or a list aligned with the segments;
+        force_len: an int or a list.  A failing segment raises where it fails; the chunks yielded before stand."""
+        from cv2amd import join as J
+        inputs = list(inputs)
+        k = len(inputs)
+        if join is None or join.is_default():
+            raise ValueError('tts_continuous: no join settings (a call without them is tts())')
+        J.check_continuous(join)                                              # out-of-range settings: refused before any work
+        if not 2 <= k <= J.MAX_PIECES:
+            raise ValueError(f'tts_continuous: {k} segments, 2 .. {J.MAX_PIECES} can be streamed as one')
+        for kw in inputs:
+            if not isinstance(kw.get('text'), torch.Tensor) or ('source_speech_token' in kw and kw['source_speech_token'].shape[1] != 0):
+                raise TypeError('tts_continuous: every segment needs a tensor of token ids as its text (no generator text, no voice conversion)')
+        if speed != 1.0:
+            S.check_speed(speed)
+        if output_sample_rate is not None:
+            O.check_rate(output_sample_rate)
+        samplings = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * k
+        force_lens = list(force_len) if isinstance(force_len, (list, tuple)) else [force_len] * k
+        if len(samplings) != k or len(force_lens) != k:
+            raise ValueError('tts_continuous: sampling / force_len lists must have one entry per segment')
+        samplings = [None if s is None or s.is_default() else s.check() for s in samplings]
+        if solver is not None:
+            solver = None if solver.is_default() else solver.check()
+        out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
+        torch.cuda.set_device(self.device)
+        call_id, segs, ahead_exc = str(uuid.uuid1()), [None] * k, {}
+        ws = J.WaveStream(join, k, self.device)
+        ox = self._Out(out_rate, pcm16, self.device) if (pcm16 or out_rate != O.MODEL_RATE) else None
+        with self.lock:
+            self.cont_dict[call_id] = ws
+        try:
+            for i in range(k):
+                if i in ahead_exc:
+                    raise ahead_exc[i]
+                if segs[i] is None:                                           # (no slot was free for the look-ahead: this segment holds none now)
+                    segs[i] = self._seg_open(inputs[i], samplings[i], force_lens[i], solver, speed, wait=True)
+                sg = segs[i]
+                if sg.exc is not None:
+                    raise sg.exc
+                with self.lock:
+                    self._ahead.discard(sg.slot)
+
+                def ahead(j=i + 1):
+                    if j < k and segs[j] is None and j not in ahead_exc:
+                        try:
+                            segs[j] = self._seg_open(inputs[j], samplings[j], force_lens[j], solver, speed, wait=False)
+                        except Exception as e:                                 # (it has closed what it opened) kept for segment j's turn
+                            ahead_exc[j] = e
+                        if segs[j] is not None:
+                            self._seg_ahead(segs[j])
+                for wav, final in self._stream_chunks(sg.uuid, sg.slot, sg.text, sg.prompt_text, sg.llm_ptok, sg.fpt, sg.feat, sg.femb, sg.pkey,
+                                                      sg.force_len, sg.sampling, speed, time.perf_counter(), prefilled=sg.prefilled,
+                                                      on_llm_end=ahead, keep_dev=True):
+                    last = final and i == k - 1
+                    with self.run_lock:                                       # the seam: gate, the one record copy, emit; then the call's output stage
+                        out = ws.chunk(wav, final).unsqueeze(0)
+                        if ox is not None:
+                            out = self._out_convert([(ox, out, last)])[0]
+                        out = out.cpu()
+                    res = {'tts_speech': out, 'segment': i}
+                    if last:
+                        res['segments'] = list(ws.plan.spans)
+                    yield res
+                segs[i] = None
+                self._close_stream_call(sg.uuid, sg.slot)                      # (before the next segment may have to wait for a slot)
+        finally:
+            for sg in segs:                                                   # an abandoned or failed call: the segment in work and the one looked ahead
+                if sg is not None:
+                    self._close_stream_call(sg.uuid, sg.slot)
+            with self.lock:
+                self.cont_dict.pop(call_id, None)
+            ws.close()
+
     # ---- model.py:336-401 -------------------------------------------------------------------------------------
     def tts(self, text=torch.zeros(1, 0, dtype=torch.int32), flow_embedding=torch.zeros(0, 192), llm_embedding=torch.zeros(0, 192),
             prompt_text=torch.zeros(1, 0, dtype=torch.int32),
@@ -1441,51 +1655,15 @@ class CosyVoice2Model:
             return
         t_call = time.perf_counter()
         slot = self._enter_shared()
-        hop, la = self.token_hop_len, self.flow.pre_lookahead_len
         try:
             if self._sched_log is not None:
                 self._sched_log.append((time.perf_counter(), 'slot', dict(slot=slot)))
             text_d, ptext_d, lptok_d = text.to(dev), prompt_text.to(dev), llm_prompt_speech_token.to(dev)
             if stream is True:
-                token_offset = 0
-                prompt_token_pad = int(np.ceil(fpt.shape[1] / hop) * hop - fpt.shape[1])
-                # flow-cache capacity in frames: the forced length, else a typical 8 speech tokens per text token (grown when exceeded)
-                n_guess = force_len if force_len is not None else min(self._limits[2], 8 * int(text.shape[1]) + 64)
-                cap_hint = self.flow.token_mel_ratio * (fpt.shape[1] + n_guess)
-                pkey = None
-                if self.flow_cache and self.prompt_cache_max > 0:              # identity of the prompt: tokens + checksums of mel and embedding
-                    pkey = (tuple(flow_prompt_speech_token.flatten().tolist()), float(prompt_speech_feat.double().sum()),
-                            float(flow_embedding.double().sum()))
-                    pkey = pkey + SV.resolve(solver, self.flow)                # (a prompt's cache belongs to the t grid and guidance rate it was run under)
-                with self.lock:
-                    self._first_pending[this_uuid] = t_call
-                    self._first_need[slot] = hop + prompt_token_pad + la        # (model.py:353-357: what the first chunk waits for)
-                self._llm_start(slot, text_d, ptext_d, lptok_d, force_len, sampling)     # prefill draws token 0; the first pass of the loop below
-                while True:                                                    # requests the rest of the first chunk's tokens
-                    this_tok, finished = None, False
-                    with self.run_lock:
-                        this_token_hop_len = hop + prompt_token_pad if token_offset == 0 else hop
-                        need = token_offset + this_token_hop_len + la
-                        toks = self._llm_poll(this_uuid, slot, need)
-                        ended = self.llm_end_dict[this_uuid]
-                        if len(toks) >= need:
-                            if not ended:                                      # the next chunk's tokens beyond what is already enqueued (by this
-                                self._llm_advance(need + hop - max(len(toks), self._enq.get(slot, 0)), shared=True)    # or another stream): the burst
-                            this_tok = torch.tensor(toks[:need], dtype=torch.int32).unsqueeze(0)          # overlaps this chunk's flow + HiFT
-                        elif ended:
-                            finished = True
-                        else:
-                            self._llm_advance(need - len(toks))                # nothing in flight any more (ids above EOS are steps without a token)
-                    if this_tok is not None:
-                        speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, True, False, cap_hint, pkey,
-                                                    first_slot=slot if token_offset == 0 else None, speed=speed)
-                        token_offset += this_token_hop_len
-                        yield {'tts_speech': speech}
-                    if finished:
-                        break
-                this_tok = torch.tensor(self.tts_speech_token_dict[this_uuid], dtype=torch.int32).unsqueeze(0)
-                speech = self._chunk_submit(this_tok, fpt, feat, femb, token_offset, this_uuid, False, True, speed=speed)
-                yield {'tts_speech': speech}
+                pkey = self._prompt_key(flow_prompt_speech_token, prompt_speech_feat, flow_embedding, solver)
+                for speech, _final in self._stream_chunks(this_uuid, slot, text_d, ptext_d, lptok_d, fpt, feat, femb, pkey, force_len, sampling,
+                                                          speed, t_call):
+                    yield {'tts_speech': speech}
             else:
                 self._llm_start(slot, text_d, ptext_d, lptok_d, force_len, sampling)
                 n_min = force_len if force_len is not None else int(text.shape[1] * self.min_token_text_ratio)
@@ -1505,23 +1683,4 @@ class CosyVoice2Model:
                     speech = self._out_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed)).cpu()
                 yield {'tts_speech': speech}
         finally:
-            with self.run_lock, self.llm_lock:                                # an abandoned generator leaves a live slot behind: park it
-                with torch.cuda.stream(self.llm_stream):
-                    self.llm.park(slot)
-                self.llm_stream.synchronize()
-            with self.lock:
-                self._first_pending.pop(this_uuid, None)
-                self._first_need.pop(slot, None)
-            self._exit_shared(slot)
-            with self.lock:
-                if self._token_log is not None:
-                    self._token_log[this_uuid] = list(self.tts_speech_token_dict.get(this_uuid, []))
-                self.tts_speech_token_dict.pop(this_uuid, None)
-                self.llm_end_dict.pop(this_uuid, None)
-                self.hift_cache_dict.pop(this_uuid, None)
-                self.stretch_dict.pop(this_uuid, None)
-                self.out_dict.pop(this_uuid, None)
-                self.samp_dict.pop(this_uuid, None)
-                self.solver_dict.pop(this_uuid, None)
-                self._hift_pin.pop(this_uuid, None)
-                self._flow_caches.pop(this_uuid, None)
+            self._close_stream_call(this_uuid, slot)

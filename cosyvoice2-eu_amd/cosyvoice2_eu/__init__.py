@@ -36,6 +36,11 @@ class Cosy2EU:
         a pause between them and, with trim_db, the silences at the seams trimmed: CosyVoice2.joined."""
         return Cosy2EU(self._model.joined(pause_ms=pause_ms, trim_db=trim_db, fade_ms=fade_ms))
 
+    def continuous(self, pause_ms=None, trim_db=None, fade_ms=None) -> 'Cosy2EU':
+        """A view of this object (same model) whose stream() runs the segments of a long text as ONE stream, with a pause between them
+        and, with trim_db, the silences at the seams gated away: CosyVoice2.continuous."""
+        return Cosy2EU(self._model.continuous(pause_ms=pause_ms, trim_db=trim_db, fade_ms=fade_ms))
+
     def tts(self, text: str, prompt: str, *, speed: float = 1.0, text_frontend: bool = False) -> Tuple[torch.Tensor, int]:
         prompt_16k = load_wav(prompt, 16000)
         segments = [out['tts_speech'] for out in self._model.inference_cross_lingual(text, prompt_16k, stream=False, speed=speed,

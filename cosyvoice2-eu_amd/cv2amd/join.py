@@ -186,3 +186,201 @@ def wave_join(wavs, pieces, N, F, dst=None):
     ft = fade_table_dev(dev, F)
     L.check(lib.cv2_wave_join(arr, table.data_ptr(), k, None if ft is None else ft.data_ptr(), F, dst.data_ptr() if N else None, N, L.stream_ptr()))
     return dst
+
+
+# ---- continuous calls: the segments' chunks as ONE stream (CosyVoice2.continuous(...); DESIGN.md section 1, csrc/join_stream.hip) ------------
+MAX_STREAM_FADE_MS = 5                 # F <= 120 samples: both fades of a piece fit inside one 240-sample frame
+
+
+def check_continuous(join):
+    """ValueError for settings a continuous view does not take: Join.check(), and fade_ms 0 .. 5; returns join"""
+    join.check()
+    if join.fade_ms is not None and join.fade_ms > MAX_STREAM_FADE_MS:
+        raise ValueError(f'continuous: fade_ms {join.fade_ms} outside 0 .. {MAX_STREAM_FADE_MS}')
+    return join
+
+
+class Emit:
+    """One chunk's emission, in positions of the current segment: the samples e0 .. e1 - 1 go out, followed by n_zero zeros; a lead fade
+    starts at fade_in_at, a tail fade ends at fade_out_end (-1: none); the samples from keep_from on stay held."""
+    __slots__ = ('e0', 'e1', 'fade_in_at', 'fade_out_end', 'n_zero', 'keep_from')
+
+    def __init__(self, e0, e1, fade_in_at, fade_out_end, n_zero, keep_from):
+        self.e0, self.e1, self.fade_in_at, self.fade_out_end, self.n_zero, self.keep_from = e0, e1, fade_in_at, fade_out_end, n_zero, keep_from
+
+    @property
+    def n_out(self):
+        return self.e1 - self.e0 + self.n_zero
+
+
+class StreamPlan:
+    """The planner of a continuous call of k segments under `join`, in Python integers (the entry points check the same integers).  Per
+    chunk of the current segment: gate_range(n_new, end) -> the frames the device analyses (None: no analysis is needed), then
+    step(n_new, end, f_lo, f_hi) with the segment's first / last loud frame so far (the device's record; -1: none) -> an Emit; the state
+    advances.  The gate is causal -- frame f is loud against the running maximum R(f) over everything up to f, not against the segment's
+    peak as in .joined() -- so that nothing it decides depends on where the chunks end."""
+
+    def __init__(self, join, k):
+        if not 2 <= k <= MAX_PIECES:
+            raise ValueError(f'continuous: {k} segments, 2 .. {MAX_PIECES} can be streamed as one')
+        self.pause, self.F, self.g = check_continuous(join).resolve()
+        self.k, self.i, self.pos, self.spans = k, 0, 0, []
+        self._open()
+
+    def _open(self):
+        # n: samples received; frames: frames analysed; e: the next sample to go out = the first held one; a: the piece's start, once known
+        self.n, self.frames, self.e, self.emitted_any = 0, 0, 0, False
+        self.a = 0 if (self.g is None or self.i == 0) else None
+
+    @property
+    def done(self):
+        return self.i >= self.k
+
+    @property
+    def n_held(self):
+        return self.n - self.e
+
+    @property
+    def gated(self):
+        """the current segment still needs the device's analysis: an interior edge of it is still open"""
+        return self.g is not None and not (self.i == self.k - 1 and self.a is not None)
+
+    def gate_range(self, n_new, end):
+        if not self.gated:
+            return None
+        n = self.n + n_new
+        return self.frames, (-(-n // FRAME) if end else n // FRAME)
+
+    def step(self, n_new, end, f_lo=-1, f_hi=-1):
+        if self.done:
+            raise ValueError('continuous: the call has had its last segment')
+        if n_new < 0:
+            raise ValueError('continuous: n_new < 0')
+        i, k, F = self.i, self.k, self.F
+        gated, last = self.gated, self.i == self.k - 1
+        n = self.n + n_new
+        if gated:
+            self.frames = -(-n // FRAME) if end else n // FRAME
+            if not -1 <= f_lo <= f_hi < max(self.frames, 1) or (f_lo < 0) != (f_hi < 0):
+                raise ValueError(f'continuous: loud frames {f_lo} .. {f_hi} of {self.frames}')
+        else:
+            f_hi = -1
+        e0 = self.e
+        if self.a is None:                                                    # a piece i > 0 whose first loud frame is not known yet
+            if f_lo >= 0:
+                self.a = e0 = max(0, FRAME * f_lo - KEEP)
+            elif end:
+                self.a = 0                                                    # no loud frame at all: kept whole
+        b = None
+        if self.a is None:
+            e1 = e0
+        elif end:
+            b = n if (last or not gated or f_hi < 0) else min(n, FRAME * (f_hi + 1) + KEEP)
+            e1 = b
+        elif last or not gated:
+            e1 = n
+        else:                                                                 # the quiet run behind the last loud frame and the fade wait
+            e1 = max(e0, FRAME * (f_hi + 1) - F) if f_hi >= 0 else e0
+        fades = F > 0 and self.g is not None
+        if b is not None:
+            fades = fades and b - self.a >= 2 * F                             # the join's rule; a piece with a whole loud frame has 240 >= 2 F
+            assert fades or F == 0 or self.g is None or not self.emitted_any
+        fade_in_at = self.a if (fades and i > 0 and e1 > e0 and e0 < self.a + F) else -1
+        fade_out_end = b if (fades and b is not None and not last) else -1
+        n_zero = self.pause if (end and not last) else 0
+        em = Emit(e0, e1, fade_in_at, fade_out_end, n_zero, n if end else e1)
+        self.emitted_any = self.emitted_any or e1 > e0
+        if end:
+            self.spans.append((self.pos, self.pos + b - self.a))
+            self.pos += b - self.a + n_zero
+            self.i += 1
+            if not self.done:
+                self._open()
+        else:
+            self.n, self.e = n, e1
+        return em
+
+
+class WaveState(C.Structure):
+    """cv2_wave_state (32 bytes)"""
+    _fields_ = [('r_bits', C.c_uint32), ('c_bits', C.c_uint32)] + [(n, C.c_int32) for n in ('frames', 'f_lo', 'f_hi', 'n_held', 'held_start', 'reserved')]
+
+
+class WaveEmit(C.Structure):
+    """cv2_wave_emit (88 bytes)"""
+    _fields_ = [(n, C.c_void_p) for n in ('held', 'chunk', 'fade_table', 'dst', 'held_dst')] + [(n, C.c_int32) for n in (
+        'held_start', 'n_held', 'n_new', 'e0', 'e1', 'fade_in_at', 'fade_out_end', 'F', 'n_zero', 'keep_from', 'held_cap', 'reserved')]
+
+
+def _bind_stream(lib):
+    if getattr(lib, '_join_stream_bound', False):
+        return
+    lib.cv2_wave_gate_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_float, C.c_void_p, C.c_void_p]
+    lib.cv2_wave_emit_chunk.argtypes = [C.c_void_p, C.POINTER(WaveEmit), C.c_void_p]
+    lib._join_stream_bound = True
+
+
+class WaveStream:
+    """The device side of one continuous call: its StreamPlan, the cv2_wave_state record and the held samples (two buffers that take
+    turns, grown when a quiet run outlasts them).  chunk(wav, end) -> the 24 kHz samples [n] that go out with this chunk of the current
+    segment, on the current HIP stream: at most one cv2_wave_gate_chunk, ONE copy of its four integers to the host (the only added
+    synchronisation) and one cv2_wave_emit_chunk.  A chunk that goes out whole and unchanged with nothing held is handed on as it is.
+    into = (a 1-D float32 device tensor, position): the samples are written there instead (always by the kernel), whatever its alignment."""
+
+    def __init__(self, join, k, device):
+        import torch
+        self.plan, self.device = StreamPlan(join, k), torch.device(device)
+        self.state = torch.zeros(8, dtype=torch.int32, device=self.device)
+        self.record = torch.empty(4, dtype=torch.int32, device=self.device)
+        self.held, self.spare = None, None
+        self.f_lo = self.f_hi = -1
+        self.launches = 0                                                      # gate + emit launches so far (diagnostics / tests)
+
+    def close(self):
+        self.state = self.record = self.held = self.spare = None
+
+    def chunk(self, wav, end, into=None):
+        import torch
+        from . import lib as L
+        lib = L.lib()
+        _bind_stream(lib)
+        pl = self.plan
+        x = _flat([wav])[0]
+        n_new, h0, n_held = x.numel(), pl.e, pl.n_held
+        cur = torch.cuda.current_stream()
+        for t in (self.state, self.record, self.held, self.spare):
+            if t is not None:
+                t.record_stream(cur)                                           # (the call's previous chunk may have run on another stream)
+        seg_start = pl.n == 0 and pl.frames == 0
+        if seg_start:
+            self.f_lo = self.f_hi = -1
+        fr = pl.gate_range(n_new, end)
+        if fr is not None and (fr[1] > fr[0] or seg_start):
+            L.check(lib.cv2_wave_gate_chunk(self.state.data_ptr(), self.held.data_ptr() if n_held else None, h0, n_held,
+                                            x.data_ptr() if n_new else None, n_new, fr[0], fr[1], int(seg_start), pl.g,
+                                            self.record.data_ptr(), L.stream_ptr()))
+            self.launches += 1
+            if fr[1] > fr[0]:
+                self.f_lo, self.f_hi = self.record.cpu().tolist()[:2]         # the one copy of four integers
+        em = pl.step(n_new, end, self.f_lo, self.f_hi)
+        n_keep = h0 + n_held + n_new - em.keep_from
+        if (into is None and n_held == 0 and n_keep == 0 and em.n_zero == 0 and em.e0 == h0 and em.e1 == h0 + n_new
+                and (em.fade_in_at < 0 or em.fade_in_at + pl.F <= em.e0) and em.fade_out_end < 0):
+            return x
+        if into is None:
+            dst = torch.empty(em.n_out, dtype=torch.float32, device=self.device)
+        else:
+            dst = into[0][into[1]:into[1] + em.n_out]
+            assert dst.dtype == torch.float32 and dst.dim() == 1 and dst.numel() == em.n_out and dst.is_cuda
+        if n_keep and (self.spare is None or self.spare.numel() < n_keep):
+            self.spare = torch.empty(max(2 * n_keep, 4096), dtype=torch.float32, device=self.device)
+        ft = fade_table_dev(self.device, pl.F)
+        a = WaveEmit(self.held.data_ptr() if n_held else None, x.data_ptr() if n_new else None, None if ft is None else ft.data_ptr(),
+                     dst.data_ptr() if em.n_out else None, self.spare.data_ptr() if n_keep else None, h0, n_held, n_new, em.e0, em.e1,
+                     em.fade_in_at, em.fade_out_end, pl.F, em.n_zero, em.keep_from, self.spare.numel() if n_keep else 0, 0)
+        L.check(lib.cv2_wave_emit_chunk(self.state.data_ptr(), C.byref(a), L.stream_ptr()))
+        self.launches += 1
+        if n_keep:
+            self.held, self.spare = self.spare, self.held
+        return dst

@@ -3,7 +3,8 @@ chunks as int16 PCM, at the server's --sample_rate or the request's optional `sa
 device when the model was built with output_pcm16).  The optional form fields `seed`, `temperature`, `top_p`, `top_k` give a request its own
 sampler settings (CosyVoice2.sampler: the same seed gives the same audio whatever else the server is doing), `flow_steps` and `cfg_rate` its own
 flow solver settings (CosyVoice2.solver: Euler steps 1 .. 31, guidance rate >= 0), `pause_ms`, `trim_db` and `fade_ms` make it a joined call
-(CosyVoice2.joined: the segments of a long text as one batch and one waveform, with that pause, interior silences trimmed); values out of range answer 422.  Form / file uploads need python-multipart (as in the reference); `build_app` raises a clear error without it."""
+(CosyVoice2.joined: the segments of a long text as one batch and one waveform, with that pause, interior silences trimmed), and with `continuous` a continuous one instead
+(CosyVoice2.continuous: the segments as one stream through one resampler, the same three fields shaping its seams; the wire format is unchanged); values out of range answer 422.  Form / file uploads need python-multipart (as in the reference); `build_app` raises a clear error without it."""
 import argparse
 from typing import Optional
 import os
@@ -21,7 +22,7 @@ def generate_data(model_output):
 
 
 def request_view(cosyvoice, sample_rate=None, seed=None, temperature=None, top_p=None, top_k=None, flow_steps=None, cfg_rate=None,
-                 pause_ms=None, trim_db=None, fade_ms=None):
+                 pause_ms=None, trim_db=None, fade_ms=None, continuous=None):
     """the model at the request's rate (None: the server's) and with the request's sampler, flow solver and join settings (None: the
     model's); an unsupported rate or a setting out of range is the client's error: 422"""
     try:
@@ -30,7 +31,9 @@ def request_view(cosyvoice, sample_rate=None, seed=None, temperature=None, top_p
             cv = cv.sampler(seed=seed, temperature=temperature, top_p=top_p, top_k=top_k)
         if flow_steps is not None or cfg_rate is not None:
             cv = cv.solver(steps=flow_steps, cfg_rate=cfg_rate)
-        if any(v is not None for v in (pause_ms, trim_db, fade_ms)):
+        if continuous:                                                      # one stream with gated seams; with no other field: the default pause
+            cv = cv.continuous(pause_ms=pause_ms if any(v is not None for v in (pause_ms, trim_db, fade_ms)) else 150, trim_db=trim_db, fade_ms=fade_ms)
+        elif any(v is not None for v in (pause_ms, trim_db, fade_ms)):
             cv = cv.joined(pause_ms=pause_ms, trim_db=trim_db, fade_ms=fade_ms)
         return cv
     except ValueError as e:
@@ -46,41 +49,45 @@ def build_app(cosyvoice):
     app = FastAPI()
     app.add_middleware(CORSMiddleware, allow_origins=['*'], allow_credentials=True, allow_methods=['*'], allow_headers=['*'])
 
-    def at(sample_rate, seed=None, temperature=None, top_p=None, top_k=None, flow_steps=None, cfg_rate=None, pause_ms=None, trim_db=None, fade_ms=None):
-        return request_view(cosyvoice, sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms)
+    def at(sample_rate, seed=None, temperature=None, top_p=None, top_k=None, flow_steps=None, cfg_rate=None, pause_ms=None, trim_db=None, fade_ms=None, continuous=None):
+        return request_view(cosyvoice, sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous)
 
     @app.get('/inference_zero_shot')
     @app.post('/inference_zero_shot')
     async def inference_zero_shot(tts_text: str = Form(), prompt_text: str = Form(), prompt_wav: UploadFile = File(), sample_rate: Optional[int] = Form(None),
                                   seed: Optional[int] = Form(None), temperature: Optional[float] = Form(None), top_p: Optional[float] = Form(None),
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
-                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None)):
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms).inference_zero_shot(tts_text, prompt_text, load_wav(prompt_wav.file, 16000))))
+                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
+                                  continuous: Optional[bool] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous).inference_zero_shot(tts_text, prompt_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
 
     @app.get('/inference_cross_lingual')
     @app.post('/inference_cross_lingual')
     async def inference_cross_lingual(tts_text: str = Form(), prompt_wav: UploadFile = File(), sample_rate: Optional[int] = Form(None),
                                   seed: Optional[int] = Form(None), temperature: Optional[float] = Form(None), top_p: Optional[float] = Form(None),
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
-                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None)):
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms).inference_cross_lingual(tts_text, load_wav(prompt_wav.file, 16000))))
+                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
+                                  continuous: Optional[bool] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous).inference_cross_lingual(tts_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
 
     @app.get('/inference_instruct2')
     @app.post('/inference_instruct2')
     async def inference_instruct2(tts_text: str = Form(), instruct_text: str = Form(), prompt_wav: UploadFile = File(), sample_rate: Optional[int] = Form(None),
                                   seed: Optional[int] = Form(None), temperature: Optional[float] = Form(None), top_p: Optional[float] = Form(None),
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
-                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None)):
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms).inference_instruct2(tts_text, instruct_text, load_wav(prompt_wav.file, 16000))))
+                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
+                                  continuous: Optional[bool] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous).inference_instruct2(tts_text, instruct_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
 
     @app.get('/inference_sft')
     @app.post('/inference_sft')
     async def inference_sft(tts_text: str = Form(), spk_id: str = Form(), sample_rate: Optional[int] = Form(None),
                                   seed: Optional[int] = Form(None), temperature: Optional[float] = Form(None), top_p: Optional[float] = Form(None),
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
-                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None)):
+                                  pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
+                                  continuous: Optional[bool] = Form(None)):
         # CosyVoice2 has no SFT speakers of its own; a registered zero-shot speaker id plays that role (cli/cosyvoice.py:70-76)
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms).inference_zero_shot(tts_text, '', None, zero_shot_spk_id=spk_id)))
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous).inference_zero_shot(tts_text, '', None, zero_shot_spk_id=spk_id, stream=bool(continuous))))
     return app
 
 

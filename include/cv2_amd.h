@@ -540,6 +540,39 @@ int cv2_wave_bounds(const cv2_wave_seg* segs, const cv2_wave_seg* segs_dev, int3
 int cv2_wave_join(const cv2_wave_piece* pieces, const cv2_wave_piece* pieces_dev, int32_t k, const float* fade_table_dev, int32_t F,
                   float* dst, int32_t n_dst, void* stream);
 
+/* Continuous calls (an extension): the 24 kHz chunks of ONE call's text segments, as the streaming path produces them, written into one
+ * stream chunk by chunk -- what cv2_wave_bounds / cv2_wave_join do for whole waveforms, with a CAUSAL gate in place of the trim (the trim's
+ * threshold is relative to the segment's peak, known at its end only).  s_i[0 .. n_i) is segment i of k, delivered in chunks.
+ *
+ * cv2_wave_gate_chunk -- frames f0 .. f1 - 1 of the current segment (240 samples without overlap; the short last frame only once the
+ *   segment has ended): peak_f as for cv2_wave_bounds; C_i = the maximum of |s| over every sample of the segments before i (C_0 = 0);
+ *   R_i(f) = max(C_i, peak_0, .., peak_f); frame f is loud iff R_i(f) > 0 and peak_f >= R_i(f) * g, ONE fp32 product.  Only maxima and that
+ *   product: a host restatement gives the same integers, whatever the chunk boundaries.  seg_start = 1 on a segment's first call (C takes the
+ *   running maximum, first / last loud frame are cleared).  The segment's samples from held_start on are [held (n_held) | chunk (n_new)];
+ *   240 f0 >= held_start.  record_dev [4] receives (first loud frame of the segment so far or -1, last loud frame or -1, f1, the bits of R);
+ *   the same values stay in *state_dev.  One block; f0 == f1 is allowed.
+ * cv2_wave_emit_chunk -- one launch writes dst[0 .. e1 - e0 + n_zero) = the segment's samples e0 .. e1 - 1 followed by n_zero samples +0.0f,
+ *   and held_dst[0 ..) = the samples from keep_from on (what stays held, compacted; held_dst is another buffer than held).  A sample q of
+ *   [fade_in_at, fade_in_at + F) is multiplied by w[q - fade_in_at], one of [fade_out_end - F, fade_out_end) by w[fade_out_end - 1 - q]
+ *   (w, F as for cv2_wave_join; -1: no such fade): ONE fp32 multiply; every other sample is copied bit for bit.  dst and held_dst are
+ *   aligned to 4 bytes only.  Checked here (-1 and cv2_last_error otherwise, nothing launched): held_start <= e0 <= e1 <= keep_from <=
+ *   held_start + n_held + n_new <= 2^30; 0 <= F <= 120; a tail fade ends at e1 and lies inside the emission, the fades do not overlap;
+ *   what stays fits held_cap; no two of dst, held_dst and the sources overlap.
+ * *state_dev (32 bytes, zeroed by the caller when the call starts) is written by these kernels only.  `a` is read on the host.
+ * Adding these entry points changed no existing struct and no signature: CV2_ABI_VERSION stays. */
+typedef struct {
+    uint32_t r_bits, c_bits;                     /* bits of the running maximum R (R includes C_i: the gate reads r_bits only) and of C_i (kept for inspection) */
+    int32_t frames, f_lo, f_hi;                  /* frames of the segment analysed; its first / last loud frame so far, -1: none */
+    int32_t n_held, held_start, reserved;        /* the held samples: how many, and the segment position of the first */
+} cv2_wave_state;                                                    /* 32 bytes */
+typedef struct {
+    const float* held; const float* chunk; const float* fade_table; float* dst; float* held_dst;
+    int32_t held_start, n_held, n_new, e0, e1, fade_in_at, fade_out_end, F, n_zero, keep_from, held_cap, reserved;
+} cv2_wave_emit;                                                     /* 88 bytes */
+int cv2_wave_gate_chunk(cv2_wave_state* state_dev, const float* held, int32_t held_start, int32_t n_held, const float* chunk, int32_t n_new,
+                        int32_t f0, int32_t f1, int32_t seg_start, float g, int32_t* record_dev, void* stream);
+int cv2_wave_emit_chunk(cv2_wave_state* state_dev, const cv2_wave_emit* a, void* stream);
+
 /* =====================================================================================================================
  * Prompt features (the extractor that feeds this path): replaces the reference's
  *   feat_extractor = matcha.utils.audio.mel_spectrogram(n_fft 1920, num_mels 80, sampling_rate 24000, hop_size 480, win_size 1920,
