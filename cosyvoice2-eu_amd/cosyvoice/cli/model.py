@@ -41,6 +41,7 @@ from cv2amd.llm import LLMEngine, MODE_RAS, MODE_GREEDY
 from cv2amd import lib as L
 from cv2amd import stretch as S
 from cv2amd import outrate as O
+from cv2amd import level as LV
 from cv2amd import sampling as SP
 from cv2amd import solver as SV
 
@@ -155,6 +156,7 @@ class CosyVoice2Model:
         self.hift_cache_dict = {}
         self.stretch_dict = {}                 # uuid -> _Stretcher of a streaming call with speed != 1; created and dropped with hift_cache_dict[uuid]
         self.out_dict = {}                     # uuid -> _Out of a call with output_sample_rate / pcm16; created and dropped with hift_cache_dict[uuid]
+        self.level_dict = {}                   # uuid -> _Level of a call with level settings; created and dropped with hift_cache_dict[uuid] (a continuous call: ONE, under the call's id)
         self.samp_dict = {}                    # uuid -> [Sampling, vocoder invocations so far] of a call with its own sampler settings / seed; likewise
         self.cont_dict = {}                    # call id -> cv2amd.join.WaveStream of a continuous call (tts_continuous): device state record and held samples
         self.solver_dict = {}                  # uuid -> cv2amd.solver.Solver of a call with its own flow steps / guidance rate; likewise
@@ -367,6 +369,78 @@ class CosyVoice2Model:
             sx.state.commit(n_new, n_emit, first_needed, finalize)
         return bufs
 
+    class _Level:
+        """A call with level settings: the planner's counters (cv2amd/level.py), the resolved gain / ceiling / peak target, the weight
+        table of its look-ahead and the retained source samples on the device."""
+        __slots__ = ('state', 'tail', 'G', 'c', 'T', 'weights')
+
+        def __init__(self, level, device):
+            self.G, self.c, L, self.T = level.resolve()
+            self.state, self.tail = LV.LevelState(L), None
+            self.weights = LV.weight_table(device, L)
+
+    def _level_convert(self, jobs):
+        """The level stage of what _mel2wav / token2wav produced, after fade and trim and immediately before the
+        output conversion.  jobs: [(_Level, waveform [1, n] fp32 on the device, finalize)], one per call; returns the [1, n_emit] float32
+        device tensors, all jobs in ONE launch on the current stream.  Calls with a peak target (whole signals only) add one peak launch
+        ahead of it; the level kernel reads the peaks from device memory, the host never does.  The planner's integers are host arithmetic,
+        the samples never leave the device.  The states advance only when the launch has succeeded."""
+        cur, args, dsts, plans, xs = torch.cuda.current_stream(), [], [], [], []
+        for lx, wav, finalize in jobs:
+            x = wav.reshape(-1)
+            if lx.T is not None and not (finalize and lx.state.consumed == 0):
+                raise ValueError('level: a peak target needs the whole signal in one piece')
+            xs.append(x if (x.numel() <= 1 or x.stride(0) == 1) else x.contiguous())
+        pk = [i for i, (lx, _w, _f) in enumerate(jobs) if lx.T is not None]
+        peaks = LV.level_peaks([xs[i] for i in pk], device=self.device) if pk else None
+        for i, ((lx, wav, finalize), x) in enumerate(zip(jobs, xs)):
+            st = lx.state
+            n0, n_emit, first_needed = LV.plan(st, x.numel(), finalize)
+            dst = torch.empty(n_emit, dtype=torch.float32, device=wav.device)
+            if lx.tail is not None:
+                lx.tail.record_stream(cur)                                     # (built on the stream of the call's previous round)
+            peak = peaks[pk.index(i):pk.index(i) + 1] if lx.T is not None else None
+            args.append(LV.level_args(st, lx.G, lx.c, lx.tail, x, dst, n0, n_emit, finalize, lx.weights, peak, lx.T))
+            dsts.append(dst)
+            plans.append((x, n_emit, first_needed))
+        LV.level_chunks(args, device=self.device)
+        for (lx, _w, finalize), (x, n_emit, first_needed) in zip(jobs, plans):
+            drop, nt = first_needed - lx.state.first, lx.state.n_tail          # samples of [tail, new] no later output reads
+            if finalize or first_needed == lx.state.consumed + x.numel():
+                lx.tail = None
+            elif drop >= nt:
+                lx.tail = x[drop - nt:].clone()
+            else:
+                lx.tail = torch.cat([lx.tail[drop:], x])
+            lx.state.commit(x.numel(), n_emit, first_needed, finalize)
+        return [d.unsqueeze(0) for d in dsts]
+
+    def _level_one(self, uuid, wav):
+        """the one waveform of a non-streaming call on its way to the output stage"""
+        lx = self.level_dict.get(uuid)
+        return wav if lx is None else self._level_convert([(lx, wav, True)])[0]
+
+    def _level_chunks(self, grp, ws):
+        """The chunks of one round on their way to the output stage: those of calls with level settings (level_dict) are levelled, all in
+        ONE cv2_level_chunk_batch launch; the others are handed on as they are."""
+        idx = [i for i, (c, w) in enumerate(zip(grp, ws)) if w is not None and c.uuid in self.level_dict]
+        if not idx:
+            return ws
+        ws, jobs = list(ws), [(self.level_dict[grp[i].uuid], ws[i], grp[i].finalize) for i in idx]
+        try:
+            res = self._level_convert(jobs)
+        except Exception:                                                      # find the offender (nothing was committed): one by one
+            res = []
+            for i, j in zip(idx, jobs):
+                try:
+                    res.append(self._level_convert([j])[0])
+                except Exception as e:
+                    grp[i].exc = e
+                    res.append(None)
+        for i, r in zip(idx, res):
+            ws[i] = r
+        return ws
+
     class _Out:
         """A call with output_sample_rate / pcm16: the planner's counters (cv2amd/outrate.py), the filter table of its rate and the
         retained source samples on the device."""
@@ -569,7 +643,7 @@ class CosyVoice2Model:
                 pool, main, sp = self.hift_pool, torch.cuda.current_stream(), []
                 batched = self._chunks_batched_hift(grp, mels) if (key[0] and not key[1]) else None
                 if batched is not None:                                        # one vocoder call per chunk shape instead of one per chunk
-                    for c, w in zip(grp, self._out_chunks(grp, batched)):
+                    for c, w in zip(grp, self._out_chunks(grp, self._level_chunks(grp, batched))):
                         if w is not None:
                             c.speech = w if c.keep_dev else w.cpu()      # (a continuous call's chunk meets its seam on the device first)
                     continue
@@ -594,7 +668,7 @@ class CosyVoice2Model:
                 for w in sp:
                     if w is not None:
                         w.record_stream(main)
-                for c, w in zip(grp, self._out_chunks(grp, sp)):
+                for c, w in zip(grp, self._out_chunks(grp, self._level_chunks(grp, sp))):
                     if w is not None:
                         c.speech = w if c.keep_dev else w.cpu()
         except BaseException as e:                                            # not attributable to one chunk: every waiting stream sees it
@@ -908,7 +982,7 @@ class CosyVoice2Model:
 
     # ---- coalesced non-streaming calls ---------------------------------------------------------------------------
     class _Pending:
-        __slots__ = ('text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'speed', 'uuid', 'done', 'speech', 'exc', 'force_len', 'dev_out', 'out', 'sampling')
+        __slots__ = ('text', 'prompt_text', 'llm_ptok', 'fpt', 'feat', 'femb', 'speed', 'uuid', 'done', 'speech', 'exc', 'force_len', 'dev_out', 'out', 'sampling', 'level')
 
     def _run_batch(self, batch):
         """llm_job + token2wav(finalize=True) of model.py:118-139,300-334 for several queued calls at once.  Only the caller whose
@@ -952,8 +1026,21 @@ class CosyVoice2Model:
             vs = [self._vocoder_seed(p.uuid) for p, _ in good]
             outs = self.hift_pool.inference_many(gm, seeds=None if all(v is None for v in vs) else vs) if gm else []
             torch.cuda.synchronize(self.device)
+            lj = [(k, (p.level, wav, True)) for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)) if p.level is not None]
+            if lj:                                                            # every levelled waveform of the batch in ONE launch (ragged lengths;
+                lev = {}                                                      # peak targets: one peak launch ahead of it, no synchronisation between)
+                try:
+                    lev = dict(zip([k for k, _ in lj], self._level_convert([j for _, j in lj])))
+                except Exception:                                              # find the offender (nothing was committed): one by one
+                    for k, j in lj:
+                        try:
+                            lev[k] = self._level_convert([j])[0]
+                        except Exception as e:
+                            good[k][0].exc = e
+                outs = [(lev.get(k), s_) if p.level is not None else (wav, s_) for k, ((p, _), (wav, s_)) in enumerate(zip(good, outs))]
+                torch.cuda.synchronize(self.device)
             conv = {}
-            cj = [(k, (p.out, wav, True)) for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)) if p.out is not None]
+            cj = [(k, (p.out, wav, True)) for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)) if p.out is not None and wav is not None]
             if cj:                                                            # every converted waveform of the batch in ONE launch (ragged lengths)
                 try:
                     conv = dict(zip([k for k, _ in cj], self._out_convert([j for _, j in cj])))
@@ -968,6 +1055,8 @@ class CosyVoice2Model:
                 if p.out is not None:
                     if k in conv:
                         p.speech = conv[k] if p.dev_out else conv[k].cpu()
+                    continue
+                if wav is None:                                               # (its level stage failed: the call has its exception)
                     continue
                 p.speech = wav.clone() if p.dev_out else wav.cpu()      # (device_output: the waveform stays in HBM for a device-side consumer)
         except BaseException as e:                                            # not attributable to one request
@@ -1023,20 +1112,22 @@ class CosyVoice2Model:
             self.hift_cache_dict.pop(this_uuid, None)
             self.stretch_dict.pop(this_uuid, None)
             self.out_dict.pop(this_uuid, None)
+            self.level_dict.pop(this_uuid, None)
             self.samp_dict.pop(this_uuid, None)
             self.solver_dict.pop(this_uuid, None)
         self._hift_pin.pop(this_uuid, None)
         self._flow_caches.pop(this_uuid, None)
 
     def tts_joined(self, inputs, join, speed=1.0, force_len=None, device_output=False, output_sample_rate=None, pcm16=False, sampling=None,
-                   solver=None):
+                   solver=None, level=None):
         """A joined call (an extension, non-streaming only): the text segments of ONE call -- `inputs`, the list of
         per-segment keyword dicts tts() takes -- queued together, so that they run as one coalesced batch (several when there are more than
         `max_batch`; other callers' requests may share them), their 24 kHz waveforms joined on the device under `join` (a cv2amd.join.Join:
         pause, optional trim of interior silences with a fade) and converted / copied to the host ONCE.  A generator that yields one dict:
         {'tts_speech': [1, n], 'segments': [(start, end), ...]}, start / end of every segment in the joined 24 kHz signal (before the output
         conversion).  sampling: one Sampling or a list aligned with the segments; force_len: an int or a list.  If a segment fails, the first
-        failure in segment order is raised and nothing is yielded.  The test hooks of single calls (_noise_hook, _trace) are not consulted."""
+        failure in segment order is raised and nothing is yielded.  The test hooks of single calls (_noise_hook, _trace) are not consulted.
+        level: a cv2amd.level.Level -- the level stage runs ONCE, on the joined waveform (a peak target is the joined signal's peak)."""
         from cv2amd import join as J
         inputs = list(inputs)
         k = len(inputs)
@@ -1057,6 +1148,7 @@ class CosyVoice2Model:
         samplings = [None if s is None or s.is_default() else s.check() for s in samplings]
         if solver is not None:
             solver = None if solver.is_default() else solver.check()
+        level = LV.check(level)
         out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
         torch.cuda.set_device(self.device)
         dev, ps = self.device, []
@@ -1082,7 +1174,7 @@ class CosyVoice2Model:
                 p.feat = kw.get('prompt_speech_feat', torch.zeros(1, 0, 80)).to(dev)
                 p.femb = kw.get('flow_embedding', torch.zeros(0, 192)).to(dev)
                 p.speed, p.force_len, p.sampling = speed, fl, sp
-                p.dev_out, p.out = True, None                                  # the waveform stays on the device; converted once, after the join
+                p.dev_out, p.out, p.level = True, None, None                   # the waveform stays on the device; levelled and converted once, after the join
             with self.lock:                                                   # adjacent and in order
                 self._pending.extend(ps)
             self._coalesce_wait(ps)
@@ -1097,6 +1189,8 @@ class CosyVoice2Model:
                     bounds = J.wave_bounds(wavs, g)[0].cpu().tolist()          # the one copy of 2 k integers
                 pieces, N, spans = J.plan([w.shape[1] for w in wavs], bounds, join)
                 speech = J.wave_join(wavs, pieces, N, F).unsqueeze(0)
+                if level is not None:
+                    speech = self._level_convert([(self._Level(level, dev), speech, True)])[0]
                 if pcm16 or out_rate != O.MODEL_RATE:
                     speech = self._out_convert([(self._Out(out_rate, pcm16, dev), speech, True)])[0]
                 if device_output:
@@ -1339,7 +1433,7 @@ class CosyVoice2Model:
                 pull(1 << 30)
                 with self.run_lock:
                     this_tok = torch.tensor(list(toks), dtype=torch.int32).unsqueeze(0)
-                    speech = self._out_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed)).cpu()
+                    speech = self._out_one(this_uuid, self._level_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed))).cpu()
                 yield {'tts_speech': speech}
         finally:
             if incoming:
@@ -1357,6 +1451,7 @@ class CosyVoice2Model:
                 self.hift_cache_dict.pop(this_uuid, None)
                 self.stretch_dict.pop(this_uuid, None)
                 self.out_dict.pop(this_uuid, None)
+                self.level_dict.pop(this_uuid, None)
                 self.samp_dict.pop(this_uuid, None)
                 self.solver_dict.pop(this_uuid, None)
                 self._hift_pin.pop(this_uuid, None)
@@ -1433,6 +1528,7 @@ class CosyVoice2Model:
             self.hift_cache_dict.pop(this_uuid, None)
             self.stretch_dict.pop(this_uuid, None)
             self.out_dict.pop(this_uuid, None)
+            self.level_dict.pop(this_uuid, None)
             self.samp_dict.pop(this_uuid, None)
             self.solver_dict.pop(this_uuid, None)
             self._hift_pin.pop(this_uuid, None)
@@ -1488,7 +1584,7 @@ class CosyVoice2Model:
         except Exception as e:
             sg.exc = e
 
-    def tts_continuous(self, inputs, join, speed=1.0, force_len=None, output_sample_rate=None, pcm16=False, sampling=None, solver=None):
+    def tts_continuous(self, inputs, join, speed=1.0, force_len=None, output_sample_rate=None, pcm16=False, sampling=None, solver=None, level=None):
         """A continuous call (an extension, streaming only): the text segments of ONE call -- `inputs`, the list of
         per-segment keyword dicts tts() takes -- streamed in order as one generator and ONE 24 kHz signal: piece 0, `pause` zeros, piece
         1, ...; with trim_db the silences at interior edges are gated away and the gated edges fade (cv2amd.join.StreamPlan; the gate is
@@ -1497,7 +1593,8 @@ class CosyVoice2Model:
         while this one's last chunks run; flow and vocoder chunks run in segment order.  The call has ONE output record: the stream is the
         conversion of the whole signal.  Yields {'tts_speech': chunk, 'segment': i}; the last chunk adds 'segments': [(start, end), ...],
         the pieces' positions in the 24 kHz signal.  A chunk may be empty.  sampling: one Sampling or a list aligned with the segments;
-        force_len: an int or a list.  A failing segment raises where it fails; the chunks yielded before stand."""
+        force_len: an int or a list.  A failing segment raises where it fails; the chunks yielded before stand.  level: a cv2amd.level.Level
+        (no peak target: the call streams) -- ONE level record over the whole signal, between the seam and the output record."""
         from cv2amd import join as J
         inputs = list(inputs)
         k = len(inputs)
@@ -1520,13 +1617,17 @@ class CosyVoice2Model:
         samplings = [None if s is None or s.is_default() else s.check() for s in samplings]
         if solver is not None:
             solver = None if solver.is_default() else solver.check()
+        level = LV.check(level, stream=True)
         out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
         torch.cuda.set_device(self.device)
         call_id, segs, ahead_exc = str(uuid.uuid1()), [None] * k, {}
         ws = J.WaveStream(join, k, self.device)
         ox = self._Out(out_rate, pcm16, self.device) if (pcm16 or out_rate != O.MODEL_RATE) else None
+        lx = self._Level(level, self.device) if level is not None else None
         with self.lock:
             self.cont_dict[call_id] = ws
+            if lx is not None:
+                self.level_dict[call_id] = lx
         try:
             for i in range(k):
                 if i in ahead_exc:
@@ -1553,6 +1654,8 @@ class CosyVoice2Model:
                     last = final and i == k - 1
                     with self.run_lock:                                       # the seam: gate, the one record copy, emit; then the call's output stage
                         out = ws.chunk(wav, final).unsqueeze(0)
+                        if lx is not None:
+                            out = self._level_convert([(lx, out, last)])[0]
                         if ox is not None:
                             out = self._out_convert([(ox, out, last)])[0]
                         out = out.cpu()
@@ -1568,6 +1671,7 @@ class CosyVoice2Model:
                     self._close_stream_call(sg.uuid, sg.slot)
             with self.lock:
                 self.cont_dict.pop(call_id, None)
+                self.level_dict.pop(call_id, None)
             ws.close()
 
     # ---- model.py:336-401 -------------------------------------------------------------------------------------
@@ -1576,7 +1680,7 @@ class CosyVoice2Model:
             llm_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             flow_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
             prompt_speech_feat=torch.zeros(1, 0, 80), source_speech_token=torch.zeros(1, 0, dtype=torch.int32), stream=False, speed=1.0,
-            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, sampling=None, solver=None, **kwargs):
+            force_len=None, device_output=False, output_sample_rate=None, pcm16=False, level=None, sampling=None, solver=None, **kwargs):
         """force_len (an extension; the reference swallows unknown keywords in **kwargs): synthetic-weights mode of SURVEY.md §8(d) —
         exactly that many speech tokens, EOS and fill ids never drawn — so that benchmark work is deterministic without a checkpoint.
         device_output (an extension, non-streaming coalesced calls only): 'tts_speech' stays on the model's device instead of the reference's
@@ -1589,7 +1693,11 @@ class CosyVoice2Model:
         chunk) alone, whatever slot, batch or round serves it.  None, or nothing set: the model's sampler and counter seed.
         solver (an extension, every mode): a cv2amd.solver.Solver -- the call's own flow solver settings: Euler steps (1 .. 31) and guidance
         rate (>= 0).  Calls with different rates share flow launches, calls with different step counts run in launches of their own
-        (DESIGN.md section 1).  None, or nothing set: the model's (cosyvoice2.yaml) on exactly the path without it."""
+        (DESIGN.md section 1).  None, or nothing set: the model's (cosyvoice2.yaml) on exactly the path without it.
+        level (an extension, every mode): a cv2amd.level.Level -- the call's own output level: a fixed gain, a peak target (non-streaming
+        only: ValueError with stream=True) and a look-ahead limiter under a ceiling, on the device just ahead of the output conversion; a
+        stream's chunks concatenate to the levelling of the whole call and run lookahead_ms behind the vocoder, so a non-final chunk may be
+        empty.  None, or nothing set: no level stage, exactly the path without it."""
         from collections.abc import Generator
         vc = source_speech_token.shape[1] != 0                   # vc_job (model.py:141-143): the tokens are given, no LLM
         bistream = isinstance(text, Generator)                    # llm_job's bistream branch (model.py:120-128)
@@ -1603,6 +1711,7 @@ class CosyVoice2Model:
             sampling = None if sampling.is_default() else sampling.check()      # out-of-range settings: refused before any work
         if solver is not None:
             solver = None if solver.is_default() else solver.check()
+        level = LV.check(level, stream is True)                              # out-of-range settings, a peak target on a stream: refused before any work
         out_rate = O.MODEL_RATE if output_sample_rate is None else output_sample_rate
         this_uuid = str(uuid.uuid1())
         # the current device is per thread and a new thread starts on device 0: callers run tts() from pool threads (the evaluation
@@ -1621,6 +1730,8 @@ class CosyVoice2Model:
                 self.stretch_dict[this_uuid] = self._Stretcher(speed)
             if pcm16 or out_rate != O.MODEL_RATE:
                 self.out_dict[this_uuid] = self._Out(out_rate, pcm16, self.device)
+            if level is not None:
+                self.level_dict[this_uuid] = self._Level(level, self.device)
             if sampling is not None:
                 self.samp_dict[this_uuid] = [sampling, 0]
             if solver is not None:
@@ -1647,6 +1758,7 @@ class CosyVoice2Model:
             p.text, p.prompt_text, p.llm_ptok = text.to(dev), prompt_text.to(dev), llm_prompt_speech_token.to(dev)
             p.fpt, p.feat, p.femb, p.speed, p.uuid, p.force_len = fpt, feat, femb, speed, this_uuid, force_len
             p.dev_out, p.out, p.sampling = bool(device_output), self.out_dict.get(this_uuid), sampling
+            p.level = self.level_dict.get(this_uuid)
             p.done, p.speech, p.exc = threading.Event(), None, None
             try:
                 yield {'tts_speech': self._tts_coalesced(p)}
@@ -1680,7 +1792,7 @@ class CosyVoice2Model:
                         break
                 with self.run_lock:
                     this_tok = torch.tensor(toks, dtype=torch.int32).unsqueeze(0)
-                    speech = self._out_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed)).cpu()
+                    speech = self._out_one(this_uuid, self._level_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed))).cpu()
                 yield {'tts_speech': speech}
         finally:
             self._close_stream_call(this_uuid, slot)

@@ -573,6 +573,42 @@ int cv2_wave_gate_chunk(cv2_wave_state* state_dev, const float* held, int32_t he
                         int32_t f0, int32_t f1, int32_t seg_start, float g, int32_t* record_dev, void* stream);
 int cv2_wave_emit_chunk(cv2_wave_state* state_dev, const cv2_wave_emit* a, void* stream);
 
+/* Output level of a call (an extension: the reference hands back whatever level its prompt gives it): a fixed gain, an optional scaling of the
+ * call's peak to a target, and a look-ahead limiter under a ceiling, on the device, AHEAD of cv2_out_resample, chunk-invariant when streaming.
+ * s[0 .. N) are the 24 kHz samples that reach the output stage (after fade and trim; the joined waveform; the one signal of a continuous
+ * call).  All fp32.  G = float32(10 ** (gain_db / 20)), c = float32(10 ** (ceiling_db / 20)), T = float32(10 ** (peak_db / 20)), each computed
+ * in fp64 on the host and rounded once; L = look-ahead in samples, 24 .. 240; w[j] = h_j / sum h, h_j = 0.5 - 0.5 cos(2 pi (j + 0.5) / (L + 1)),
+ * j = 0 .. L (fp64, rounded once).  Ge = G, or with a peak target P = max |s[n]| (NaN counts as 0): Ge = fl(G * fl(T / P)) when P > 0.
+ *     x[n] = fl(Ge s[n]);   a[n] = |x[n]|, NaN counts as 0;   r[n] = a[n] > c ? fl(c / a[n]) : 1;   d[n] = a[n] > c ? fl(1 - r[n]) : 0
+ *     D[n] = max d[k], k = n .. min(n + L, N - 1)
+ *     acc[n] = sum over j = 0 .. L with n - j >= 0 of w[j] D[n - j]       ONE fp32 fmaf chain in ascending j from 0.f
+ *     g[n] = max(0, min(fl(1 - acc[n]), r[n]));   y[n] = clamp(fl(g[n] x[n]), -c, c);   a NaN x[n] gives +0, an infinite one +-c
+ * |y| <= c always; where no sample within +-L of n is over the ceiling acc is exactly 0 and y[n] = x[n] (= s[n] bit for bit when Ge = 1);
+ * N samples in, N out, no index delay.  Before the final chunk sample n goes out as soon as n + L <= n_available - 1; the final chunk emits
+ * the rest.  Retained per call: the source samples from max(0, n_next - L) on (at most 2 L).  cv2amd/level.py plans the integers.
+ * One record = one call's chunk: the source samples first .. n_avail - 1 as two pieces, `tail` (n_tail samples from global index `first` on)
+ * and `fresh` (the n_avail - first - n_tail new ones), both fp32 device, aligned to 4 bytes only; the outputs n0 .. n0 + n_emit - 1 go to
+ * dst[0 .. n_emit) (fp32 device, aligned to 4 bytes only; dst_cap = samples it can take).  n_final: -1 while more samples will come, else
+ * = n_avail.  weights = w (device, L + 1 floats).  peak = NULL: Ge is the gain applied; else a device float holding P (cv2_level_peak_batch
+ * ahead of this call on the same stream: the kernel reads it, the host never does), Ge holds G, T the target, n_final >= 0.  Checked here
+ * (-1 and cv2_last_error otherwise, nothing launched): L in 24 .. 240; 0 < c <= 1; 0 < Ge <= 16; 0 < T <= c; the counts; max(0, n0 - L) >=
+ * first; n0 + n_emit - 1 + L <= n_avail - 1 before the final chunk, n0 + n_emit <= n_final in it; n_emit <= dst_cap.  Records of one batch
+ * may differ in every field.
+ * cv2_level_peak_batch -- peaks_dev[i] = max |s_i[q]| (NaN counts as 0) of n signals (cv2_wave_seg records, on the host and in device memory
+ * as for cv2_wave_bounds; a length of 0 gives 0): a clear of peaks_dev and one launch, an integer atomicMax on the bit pattern per block.
+ * Adding these entry points changed no existing struct and no signature: CV2_ABI_VERSION stays. */
+typedef struct {
+    const float* tail; const float* fresh; float* dst; const float* weights; const float* peak;
+    int32_t first, n_tail, n_avail, n_final;
+    int32_t n0, n_emit, L, dst_cap;
+    float Ge, c, T; int32_t reserved;
+} cv2_level_args;                                                    /* 88 bytes */
+int cv2_level_chunk(const cv2_level_args* a, void* stream);                       /* a: host */
+/* n calls as ONE launch (gridDim.z = n): `args` are the n records on the host (checked here), `table_dev` the same n records in device
+ * memory, uploaded by the caller ahead of this call on `stream`. */
+int cv2_level_chunk_batch(const cv2_level_args* args, const cv2_level_args* table_dev, int32_t n, void* stream);
+int cv2_level_peak_batch(const cv2_wave_seg* segs, const cv2_wave_seg* segs_dev, int32_t n, float* peaks_dev, void* stream);
+
 /* =====================================================================================================================
  * Prompt features (the extractor that feeds this path): replaces the reference's
  *   feat_extractor = matcha.utils.audio.mel_spectrogram(n_fft 1920, num_mels 80, sampling_rate 24000, hop_size 480, win_size 1920,
