@@ -197,7 +197,7 @@ class CosyVoice2:
             view.join = None
         return view
 
-    def level(self, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None):
+    def level(self, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None, loudness_lufs=None):
         """A view of this object (same model, same frontend) whose calls set their output level on the device, just ahead of the output
         conversion: what a server uses so that two zero-shot voices come out equally loud and no call clips.  gain_db = fixed gain, -24 .. 24
         (0); ceiling_db = ceiling of the look-ahead limiter in dBFS, -12 .. 0 (-1 once any field is set): no sample leaves above it, and a
@@ -212,12 +212,20 @@ class CosyVoice2:
         continuous call has one level record over its whole signal.  Measured (profiles/level.json): the level launch over 10 s of
         audio 7 / 10 / 14 us at 1 / 5 / 10 ms look-ahead, the peak launch 21 us; nothing measurable on a 10 s non-streaming call (119.3 against 119.5 ms);
         a stream's first chunk 49.1 against 48.0 ms alone, 115.6 against 112.7 ms among 8 streams, chunk gaps unchanged.  Composes with .output(), .sampler(),
-        .solver(), .joined() and .continuous()."""
+        .solver(), .joined() and .continuous().
+        loudness_lufs = scale the call to that integrated loudness (ITU-R BS.1770-4: K-weighting, 400 ms blocks, the absolute and the
+        relative gate; -16 for streaming services, -23 for EBU R 128), -40 .. -5, measured on the device over the call's 24 kHz signal (a joined
+        call: the joined signal, pauses gated out), the gain limited to +-24 dB; gain_db stacks on top, the limiter and the ceiling run
+        afterwards, so a call the limiter has to hold back ends below its target.  Non-streaming calls only, like peak_db, and not
+        together with it: ValueError.  Such a call's result carries the measured loudness of its unlevelled signal as 'loudness_lufs'
+        (a float, -inf for a call shorter than 400 ms or silent: its gain is then left alone).  Measured (DESIGN.md section 5,
+        profiles/loudness.json): the measurement 169 us for 10 s of audio, a 10 s call 118.7 against 118.3 ms."""
         import copy
         from cv2amd.level import Level
-        new = Level(gain_db=gain_db, peak_db=peak_db, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms)
+        new = Level(gain_db=gain_db, peak_db=peak_db, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms, loudness_lufs=loudness_lufs)
         if self.out_level is not None:
-            new = self.out_level.replace(gain_db=new.gain_db, peak_db=new.peak_db, ceiling_db=new.ceiling_db, lookahead_ms=new.lookahead_ms)
+            new = self.out_level.replace(gain_db=new.gain_db, peak_db=new.peak_db, ceiling_db=new.ceiling_db, lookahead_ms=new.lookahead_ms,
+                                         loudness_lufs=new.loudness_lufs)
         new.check()
         if self.stream_join is not None:
             new.check_stream(True)                                          # (a continuous view streams)

@@ -42,6 +42,7 @@ from cv2amd import lib as L
 from cv2amd import stretch as S
 from cv2amd import outrate as O
 from cv2amd import level as LV
+from cv2amd import loudness as LD
 from cv2amd import sampling as SP
 from cv2amd import solver as SV
 
@@ -371,35 +372,51 @@ class CosyVoice2Model:
 
     class _Level:
         """A call with level settings: the planner's counters (cv2amd/level.py), the resolved gain / ceiling / peak target, the weight
-        table of its look-ahead and the retained source samples on the device."""
-        __slots__ = ('state', 'tail', 'G', 'c', 'T', 'weights')
+        table of its look-ahead and the retained source samples on the device.  loud: T is a loudness target's reference amplitude, divided
+        by the measured R instead of the peak; lufs: the measured loudness of such a call, on the device until result() is asked for it."""
+        __slots__ = ('state', 'tail', 'G', 'c', 'T', 'weights', 'loud', 'lufs')
 
         def __init__(self, level, device):
             self.G, self.c, L, self.T = level.resolve()
+            self.loud, self.lufs = level.loud, None
             self.state, self.tail = LV.LevelState(L), None
             self.weights = LV.weight_table(device, L)
+
+        def result(self):
+            """what a call with a loudness target adds to its result: the measured loudness of its unlevelled signal (one float copied
+            from the device; the waveform's copy has synchronised the stream)"""
+            if self.lufs is None:
+                return {}
+            if not isinstance(self.lufs, float):
+                self.lufs = float(self.lufs.cpu())
+            return {'loudness_lufs': self.lufs}
 
     def _level_convert(self, jobs):
         """The level stage of what _mel2wav / token2wav produced, after fade and trim and immediately before the
         output conversion.  jobs: [(_Level, waveform [1, n] fp32 on the device, finalize)], one per call; returns the [1, n_emit] float32
         device tensors, all jobs in ONE launch on the current stream.  Calls with a peak target (whole signals only) add one peak launch
-        ahead of it; the level kernel reads the peaks from device memory, the host never does.  The planner's integers are host arithmetic,
+        ahead of it, calls with a loudness target one measurement enqueue (cv2_loudness_batch: R in the peaks' place, Lk kept with the
+        record); the level kernel reads the peaks from device memory, the host never does.  The planner's integers are host arithmetic,
         the samples never leave the device.  The states advance only when the launch has succeeded."""
         cur, args, dsts, plans, xs = torch.cuda.current_stream(), [], [], [], []
         for lx, wav, finalize in jobs:
             x = wav.reshape(-1)
             if lx.T is not None and not (finalize and lx.state.consumed == 0):
-                raise ValueError('level: a peak target needs the whole signal in one piece')
+                raise ValueError('level: a peak or loudness target needs the whole signal in one piece')
             xs.append(x if (x.numel() <= 1 or x.stride(0) == 1) else x.contiguous())
-        pk = [i for i, (lx, _w, _f) in enumerate(jobs) if lx.T is not None]
+        pk = [i for i, (lx, _w, _f) in enumerate(jobs) if lx.T is not None and not lx.loud]
         peaks = LV.level_peaks([xs[i] for i in pk], device=self.device) if pk else None
+        ld = [i for i, (lx, _w, _f) in enumerate(jobs) if lx.T is not None and lx.loud]
+        refs, lufs = LD.measure([xs[i] for i in ld], [jobs[i][0].T for i in ld], device=self.device) if ld else (None, None)
         for i, ((lx, wav, finalize), x) in enumerate(zip(jobs, xs)):
             st = lx.state
             n0, n_emit, first_needed = LV.plan(st, x.numel(), finalize)
             dst = torch.empty(n_emit, dtype=torch.float32, device=wav.device)
             if lx.tail is not None:
                 lx.tail.record_stream(cur)                                     # (built on the stream of the call's previous round)
-            peak = peaks[pk.index(i):pk.index(i) + 1] if lx.T is not None else None
+            peak = None
+            if lx.T is not None:
+                peak = refs[ld.index(i):ld.index(i) + 1] if lx.loud else peaks[pk.index(i):pk.index(i) + 1]
             args.append(LV.level_args(st, lx.G, lx.c, lx.tail, x, dst, n0, n_emit, finalize, lx.weights, peak, lx.T))
             dsts.append(dst)
             plans.append((x, n_emit, first_needed))
@@ -413,6 +430,8 @@ class CosyVoice2Model:
             else:
                 lx.tail = torch.cat([lx.tail[drop:], x])
             lx.state.commit(x.numel(), n_emit, first_needed, finalize)
+        for k, i in enumerate(ld):
+            jobs[i][0].lufs = lufs[k:k + 1]
         return [d.unsqueeze(0) for d in dsts]
 
     def _level_one(self, uuid, wav):
@@ -1039,6 +1058,9 @@ class CosyVoice2Model:
                             good[k][0].exc = e
                 outs = [(lev.get(k), s_) if p.level is not None else (wav, s_) for k, ((p, _), (wav, s_)) in enumerate(zip(good, outs))]
                 torch.cuda.synchronize(self.device)
+                for k, _j in lj:
+                    if k in lev:
+                        good[k][0].level.result()                              # (a loudness target: the measured Lk, copied here by the leader)
             conv = {}
             cj = [(k, (p.out, wav, True)) for k, ((p, _), (wav, _s)) in enumerate(zip(good, outs)) if p.out is not None and wav is not None]
             if cj:                                                            # every converted waveform of the batch in ONE launch (ragged lengths)
@@ -1127,7 +1149,8 @@ class CosyVoice2Model:
         {'tts_speech': [1, n], 'segments': [(start, end), ...]}, start / end of every segment in the joined 24 kHz signal (before the output
         conversion).  sampling: one Sampling or a list aligned with the segments; force_len: an int or a list.  If a segment fails, the first
         failure in segment order is raised and nothing is yielded.  The test hooks of single calls (_noise_hook, _trace) are not consulted.
-        level: a cv2amd.level.Level -- the level stage runs ONCE, on the joined waveform (a peak target is the joined signal's peak)."""
+        level: a cv2amd.level.Level -- the level stage runs ONCE, on the joined waveform (a peak target is the joined signal's peak, a
+        loudness target the joined signal's integrated loudness, which the dict then carries as 'loudness_lufs')."""
         from cv2amd import join as J
         inputs = list(inputs)
         k = len(inputs)
@@ -1189,15 +1212,17 @@ class CosyVoice2Model:
                     bounds = J.wave_bounds(wavs, g)[0].cpu().tolist()          # the one copy of 2 k integers
                 pieces, N, spans = J.plan([w.shape[1] for w in wavs], bounds, join)
                 speech = J.wave_join(wavs, pieces, N, F).unsqueeze(0)
-                if level is not None:
-                    speech = self._level_convert([(self._Level(level, dev), speech, True)])[0]
+                lx = self._Level(level, dev) if level is not None else None
+                if lx is not None:
+                    speech = self._level_convert([(lx, speech, True)])[0]
                 if pcm16 or out_rate != O.MODEL_RATE:
                     speech = self._out_convert([(self._Out(out_rate, pcm16, dev), speech, True)])[0]
                 if device_output:
                     torch.cuda.current_stream().synchronize()
                 else:
                     speech = speech.cpu()
-            yield {'tts_speech': speech, 'segments': spans}
+                extra = lx.result() if lx is not None else {}
+            yield {'tts_speech': speech, 'segments': spans, **extra}
         finally:
             with self.lock:                                                   # (an abandoned or refused call: nothing of it stays queued)
                 for p in ps:
@@ -1434,7 +1459,8 @@ class CosyVoice2Model:
                 with self.run_lock:
                     this_tok = torch.tensor(list(toks), dtype=torch.int32).unsqueeze(0)
                     speech = self._out_one(this_uuid, self._level_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed))).cpu()
-                yield {'tts_speech': speech}
+                    extra = self.level_dict[this_uuid].result() if this_uuid in self.level_dict else {}
+                yield {'tts_speech': speech, **extra}
         finally:
             if incoming:
                 with self._bi_cv:
@@ -1697,7 +1723,9 @@ class CosyVoice2Model:
         level (an extension, every mode): a cv2amd.level.Level -- the call's own output level: a fixed gain, a peak target (non-streaming
         only: ValueError with stream=True) and a look-ahead limiter under a ceiling, on the device just ahead of the output conversion; a
         stream's chunks concatenate to the levelling of the whole call and run lookahead_ms behind the vocoder, so a non-final chunk may be
-        empty.  None, or nothing set: no level stage, exactly the path without it."""
+        empty.  With loudness_lufs (non-streaming only, as peak_db) the call is scaled to that BS.1770 integrated
+        loudness, measured on the device, and its result carries the measured loudness of the unlevelled signal as 'loudness_lufs' (a
+        float, or -inf).  None, or nothing set: no level stage, exactly the path without it."""
         from collections.abc import Generator
         vc = source_speech_token.shape[1] != 0                   # vc_job (model.py:141-143): the tokens are given, no LLM
         bistream = isinstance(text, Generator)                    # llm_job's bistream branch (model.py:120-128)
@@ -1761,7 +1789,8 @@ class CosyVoice2Model:
             p.level = self.level_dict.get(this_uuid)
             p.done, p.speech, p.exc = threading.Event(), None, None
             try:
-                yield {'tts_speech': self._tts_coalesced(p)}
+                speech = self._tts_coalesced(p)
+                yield {'tts_speech': speech, **(p.level.result() if p.level is not None else {})}
             finally:
                 self._drop_call(this_uuid)
             return
@@ -1793,6 +1822,7 @@ class CosyVoice2Model:
                 with self.run_lock:
                     this_tok = torch.tensor(toks, dtype=torch.int32).unsqueeze(0)
                     speech = self._out_one(this_uuid, self._level_one(this_uuid, self.token2wav(this_tok, fpt, feat, femb, 0, this_uuid, finalize=True, speed=speed))).cpu()
-                yield {'tts_speech': speech}
+                    extra = self.level_dict[this_uuid].result() if this_uuid in self.level_dict else {}
+                yield {'tts_speech': speech, **extra}
         finally:
             self._close_stream_call(this_uuid, slot)

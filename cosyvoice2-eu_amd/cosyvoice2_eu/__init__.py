@@ -41,10 +41,11 @@ class Cosy2EU:
         and, with trim_db, the silences at the seams gated away: CosyVoice2.continuous."""
         return Cosy2EU(self._model.continuous(pause_ms=pause_ms, trim_db=trim_db, fade_ms=fade_ms))
 
-    def level(self, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None) -> 'Cosy2EU':
+    def level(self, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None, loudness_lufs=None) -> 'Cosy2EU':
         """A view of this object (same model) whose calls set their output level on the device -- a fixed gain, a peak target (tts() only)
-        and a look-ahead limiter under a ceiling: CosyVoice2.level."""
-        return Cosy2EU(self._model.level(gain_db=gain_db, peak_db=peak_db, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms))
+        and a look-ahead limiter under a ceiling, or with loudness_lufs a BS.1770 integrated-loudness target (tts() only): CosyVoice2.level."""
+        return Cosy2EU(self._model.level(gain_db=gain_db, peak_db=peak_db, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms,
+                                         loudness_lufs=loudness_lufs))
 
     def tts(self, text: str, prompt: str, *, speed: float = 1.0, text_frontend: bool = False) -> Tuple[torch.Tensor, int]:
         prompt_16k = load_wav(prompt, 16000)

@@ -1,4 +1,4 @@
-"""Host side of the output level (gain_db, peak_db, ceiling_db, lookahead_ms; DESIGN.md section 1, k_level in csrc/level.hip).
+"""Host side of the output level (gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs; DESIGN.md section 1, k_level in csrc/level.hip).
 
 A `Level` value travels with a call from the public surface (CosyVoice2.level(...)) to the stage just ahead of the output conversion.  The
 stage is defined on the global sample index of a call: with L = round(lookahead_ms * 24) sample n's gain depends on the samples n - L .. n + L,
@@ -14,19 +14,22 @@ import math
 from .sampling import f32
 
 MODEL_RATE = 24000
-FIELDS = ('gain_db', 'peak_db', 'ceiling_db', 'lookahead_ms')
-RANGES = {'gain_db': (-24, 24), 'peak_db': (-24, 0), 'ceiling_db': (-12, 0), 'lookahead_ms': (1, 10)}
+FIELDS = ('gain_db', 'peak_db', 'ceiling_db', 'lookahead_ms', 'loudness_lufs')
+RANGES = {'gain_db': (-24, 24), 'peak_db': (-24, 0), 'ceiling_db': (-12, 0), 'lookahead_ms': (1, 10), 'loudness_lufs': (-40, -5)}
 CEILING_DB, LOOKAHEAD_MS = -1.0, 5.0              # what a call with any field set runs under where these two are not
 L_MIN, L_MAX = 24, 240
 _tables = {}
 
 
 class Level:
-    """gain_db, peak_db, ceiling_db, lookahead_ms: None = not set.  With nothing set there is no level stage at all."""
+    """gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs: None = not set.  With nothing set there is no level stage at all.
+    loudness_lufs scales the call to an integrated loudness (ITU-R BS.1770-4, measured on the device: cv2amd/loudness.py) as peak_db
+    scales it to a peak; the two exclude each other."""
     __slots__ = FIELDS
 
-    def __init__(self, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None):
+    def __init__(self, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None, loudness_lufs=None):
         self.gain_db, self.peak_db, self.ceiling_db, self.lookahead_ms = gain_db, peak_db, ceiling_db, lookahead_ms
+        self.loudness_lufs = loudness_lufs
 
     def __repr__(self):
         return 'Level(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in FIELDS if getattr(self, k) is not None) + ')'
@@ -62,22 +65,39 @@ class Level:
             ceiling = CEILING_DB if self.ceiling_db is None else self.ceiling_db
             if self.peak_db > ceiling:
                 raise ValueError(f'level: peak_db {self.peak_db} above the ceiling of {ceiling} dBFS')
+        if self.loudness_lufs is not None:
+            if self.peak_db is not None:
+                raise ValueError('level: loudness_lufs and peak_db both scale the call: set one of them')
+            ceiling = CEILING_DB if self.ceiling_db is None else self.ceiling_db
+            if self.loudness_lufs + 0.691 > ceiling:                          # (k_level takes no reference amplitude above its ceiling)
+                raise ValueError(f'level: loudness_lufs {self.loudness_lufs} cannot be met under the ceiling of {ceiling} dBFS')
         return self
 
     def check_stream(self, stream):
-        """a peak target needs the call's peak, known at its end only: refused on a streaming call; returns self"""
+        """a peak or loudness target needs the whole call, known at its end only: refused on a streaming call; returns self"""
         if stream and self.peak_db is not None:
             raise ValueError('level: peak_db needs the whole signal: it is not supported with stream=True (use gain_db)')
+        if stream and self.loudness_lufs is not None:
+            raise ValueError('level: loudness_lufs needs the whole signal: it is not supported with stream=True (use gain_db)')
         return self
 
     def resolve(self):
         """-> (G, c, L, T or None) the call runs under: the gain, the ceiling and the peak target as float32 values (computed in float64,
-        rounded once), the look-ahead in samples.  Two settings that resolve to equal tuples are the same computation."""
+        rounded once), the look-ahead in samples.  Two settings that resolve to equal tuples are the same computation.  With loudness_lufs
+        T is the reference amplitude of the loudness target, float32(10 ** ((loudness_lufs + 0.691) / 20)), which the level kernel divides
+        by the measured R = sqrt(z) instead of the peak (`loud` tells the two apart)."""
         G = f32(10.0 ** ((0.0 if self.gain_db is None else self.gain_db) / 20.0))
         c = f32(10.0 ** ((CEILING_DB if self.ceiling_db is None else self.ceiling_db) / 20.0))
         L = int(round((LOOKAHEAD_MS if self.lookahead_ms is None else self.lookahead_ms) * 24))
         T = None if self.peak_db is None else min(f32(10.0 ** (self.peak_db / 20.0)), c)      # (peak_db <= ceiling_db; equal dB: equal floats)
+        if self.loudness_lufs is not None:
+            T = min(f32(10.0 ** ((self.loudness_lufs + 0.691) / 20.0)), c)
         return G, c, L, T
+
+    @property
+    def loud(self):
+        """the call is scaled to a loudness target (resolve()'s T is then divided by the measured R, not by the peak)"""
+        return self.loudness_lufs is not None
 
 
 def check(level, stream=False):

@@ -4,8 +4,8 @@ device when the model was built with output_pcm16).  The optional form fields `s
 sampler settings (CosyVoice2.sampler: the same seed gives the same audio whatever else the server is doing), `flow_steps` and `cfg_rate` its own
 flow solver settings (CosyVoice2.solver: Euler steps 1 .. 31, guidance rate >= 0), `pause_ms`, `trim_db` and `fade_ms` make it a joined call
 (CosyVoice2.joined: the segments of a long text as one batch and one waveform, with that pause, interior silences trimmed), and with `continuous` a continuous one instead
-(CosyVoice2.continuous: the segments as one stream through one resampler, the same three fields shaping its seams; the wire format is unchanged), `gain_db`, `peak_db`, `ceiling_db` and `lookahead_ms` its own
-output level (CosyVoice2.level: a fixed gain, a peak target -- not with `continuous`, which streams -- and a look-ahead limiter under a ceiling, on the device); values out of range answer 422.  Form / file uploads need python-multipart (as in the reference); `build_app` raises a clear error without it."""
+(CosyVoice2.continuous: the segments as one stream through one resampler, the same three fields shaping its seams; the wire format is unchanged), `gain_db`, `peak_db`, `ceiling_db`, `lookahead_ms` and `loudness_lufs` its own
+output level (CosyVoice2.level: a fixed gain, a peak target or a BS.1770 loudness target -- neither with `continuous`, which streams -- and a look-ahead limiter under a ceiling, on the device); values out of range answer 422.  Form / file uploads need python-multipart (as in the reference); `build_app` raises a clear error without it."""
 import argparse
 from typing import Optional
 import os
@@ -23,7 +23,8 @@ def generate_data(model_output):
 
 
 def request_view(cosyvoice, sample_rate=None, seed=None, temperature=None, top_p=None, top_k=None, flow_steps=None, cfg_rate=None,
-                 pause_ms=None, trim_db=None, fade_ms=None, continuous=None, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None):
+                 pause_ms=None, trim_db=None, fade_ms=None, continuous=None, gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None,
+                 loudness_lufs=None):
     """the model at the request's rate (None: the server's) and with the request's sampler, flow solver, join and level settings (None: the
     model's); an unsupported rate or a setting out of range is the client's error: 422"""
     try:
@@ -36,10 +37,10 @@ def request_view(cosyvoice, sample_rate=None, seed=None, temperature=None, top_p
             cv = cv.continuous(pause_ms=pause_ms if any(v is not None for v in (pause_ms, trim_db, fade_ms)) else 150, trim_db=trim_db, fade_ms=fade_ms)
         elif any(v is not None for v in (pause_ms, trim_db, fade_ms)):
             cv = cv.joined(pause_ms=pause_ms, trim_db=trim_db, fade_ms=fade_ms)
-        if any(v is not None for v in (gain_db, peak_db, ceiling_db, lookahead_ms)):
-            cv = cv.level(gain_db=gain_db, peak_db=peak_db, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms)
+        if any(v is not None for v in (gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs)):
+            cv = cv.level(gain_db=gain_db, peak_db=peak_db, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms, loudness_lufs=loudness_lufs)
             if continuous:
-                cv.out_level.check_stream(True)                             # (the endpoints stream a continuous request: no peak target)
+                cv.out_level.check_stream(True)                             # (the endpoints stream a continuous request: no peak or loudness target)
         return cv
     except ValueError as e:
         from fastapi import HTTPException
@@ -55,9 +56,9 @@ def build_app(cosyvoice):
     app.add_middleware(CORSMiddleware, allow_origins=['*'], allow_credentials=True, allow_methods=['*'], allow_headers=['*'])
 
     def at(sample_rate, seed=None, temperature=None, top_p=None, top_k=None, flow_steps=None, cfg_rate=None, pause_ms=None, trim_db=None, fade_ms=None, continuous=None,
-           gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None):
+           gain_db=None, peak_db=None, ceiling_db=None, lookahead_ms=None, loudness_lufs=None):
         return request_view(cosyvoice, sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous,
-                            gain_db, peak_db, ceiling_db, lookahead_ms)
+                            gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs)
 
     @app.get('/inference_zero_shot')
     @app.post('/inference_zero_shot')
@@ -66,8 +67,9 @@ def build_app(cosyvoice):
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
                                   pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
                                   continuous: Optional[bool] = Form(None), gain_db: Optional[float] = Form(None), peak_db: Optional[float] = Form(None),
-                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None)):
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms).inference_zero_shot(tts_text, prompt_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
+                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None),
+                                  loudness_lufs: Optional[float] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs).inference_zero_shot(tts_text, prompt_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
 
     @app.get('/inference_cross_lingual')
     @app.post('/inference_cross_lingual')
@@ -76,8 +78,9 @@ def build_app(cosyvoice):
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
                                   pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
                                   continuous: Optional[bool] = Form(None), gain_db: Optional[float] = Form(None), peak_db: Optional[float] = Form(None),
-                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None)):
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms).inference_cross_lingual(tts_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
+                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None),
+                                  loudness_lufs: Optional[float] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs).inference_cross_lingual(tts_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
 
     @app.get('/inference_instruct2')
     @app.post('/inference_instruct2')
@@ -86,8 +89,9 @@ def build_app(cosyvoice):
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
                                   pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
                                   continuous: Optional[bool] = Form(None), gain_db: Optional[float] = Form(None), peak_db: Optional[float] = Form(None),
-                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None)):
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms).inference_instruct2(tts_text, instruct_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
+                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None),
+                                  loudness_lufs: Optional[float] = Form(None)):
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs).inference_instruct2(tts_text, instruct_text, load_wav(prompt_wav.file, 16000), stream=bool(continuous))))
 
     @app.get('/inference_sft')
     @app.post('/inference_sft')
@@ -96,9 +100,10 @@ def build_app(cosyvoice):
                                   top_k: Optional[int] = Form(None), flow_steps: Optional[int] = Form(None), cfg_rate: Optional[float] = Form(None),
                                   pause_ms: Optional[float] = Form(None), trim_db: Optional[float] = Form(None), fade_ms: Optional[float] = Form(None),
                                   continuous: Optional[bool] = Form(None), gain_db: Optional[float] = Form(None), peak_db: Optional[float] = Form(None),
-                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None)):
+                                  ceiling_db: Optional[float] = Form(None), lookahead_ms: Optional[float] = Form(None),
+                                  loudness_lufs: Optional[float] = Form(None)):
         # CosyVoice2 has no SFT speakers of its own; a registered zero-shot speaker id plays that role (cli/cosyvoice.py:70-76)
-        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms).inference_zero_shot(tts_text, '', None, zero_shot_spk_id=spk_id, stream=bool(continuous))))
+        return StreamingResponse(generate_data(at(sample_rate, seed, temperature, top_p, top_k, flow_steps, cfg_rate, pause_ms, trim_db, fade_ms, continuous, gain_db, peak_db, ceiling_db, lookahead_ms, loudness_lufs).inference_zero_shot(tts_text, '', None, zero_shot_spk_id=spk_id, stream=bool(continuous))))
     return app
 
 

@@ -609,6 +609,31 @@ int cv2_level_chunk(const cv2_level_args* a, void* stream);                     
 int cv2_level_chunk_batch(const cv2_level_args* args, const cv2_level_args* table_dev, int32_t n, void* stream);
 int cv2_level_peak_batch(const cv2_wave_seg* segs, const cv2_wave_seg* segs_dev, int32_t n, float* peaks_dev, void* stream);
 
+/* Integrated loudness of a call (an extension; ITU-R BS.1770-4 at fs = 24000), measured on the device so that cv2_level_chunk can scale a call
+ * to a loudness target: csrc/loudness.hip.  s[0 .. N) are the 24 kHz fp32 samples that enter the level stage; a non-finite sample counts as 0.
+ *   K-weighting: two biquads in cascade (transposed direct form II, fp32), the shelf, then the high-pass; coefficients from the analog
+ *     prototype that reproduces the BS.1770 table at 48 kHz, in float64 on the host, rounded once; K = tan(pi f0 / fs), a0 = 1 + K / Q + K^2:
+ *     shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G / 20), Vb = Vh^0.4996667741545416,
+ *                b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0], a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *     high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1], a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *   Blocks: hop 2400 samples; block j = y[2400 j .. 2400 j + 9600), j = 0 .. J - 1, J = floor((N - 9600) / 2400) + 1 when N >= 9600, else 0;
+ *     z_j = mean y^2 over block j, l_j = -0.691 + 10 log10 z_j.
+ *   Gates: A = {j : l_j > -70}; Gamma = -0.691 + 10 log10 mean_A z_j - 10; B = {j in A : l_j > Gamma}; z = mean_B z_j; Lk = -0.691 + 10 log10 z.
+ *   No block or A empty: Lk = -inf, R = 0.  Else R = sqrt(z), with a target T > 0 clamped to [T / g_max, T g_max], g_max = float32(10^(24/20)).
+ * cv2_loudness_batch -- n signals (cv2_wave_seg records on the host, checked here, and the same records in device memory, as for
+ * cv2_level_peak_batch; sources aligned to 4 bytes only), all in one enqueue on `stream` (four launches; no allocation, no synchronisation,
+ * no atomics): R_dev[i] and lufs_dev[i] receive R and Lk of signal i.  targets / targets_dev: T per signal on the host and in device memory
+ * (0 <= T <= 1, 0: R is not clamped), or both NULL.  filter_dev: 24 floats in device memory -- shelf b0 b1 b2 a1 a2, high-pass a1 a2, 0, then
+ * M = A^2400 row-major, A the 4 x 4 transition matrix of the cascade's state (s1, s2, t1, t2) for a zero input (cv2amd/loudness.py builds it
+ * in float64).  ws: the caller's scratch for the hop states and hop energies, 16-byte aligned, at least the size that
+ * cv2_loudness_workspace_bytes gives for the same records; its contents need not be kept or cleared.  The result is a function of each
+ * signal's samples alone: bit-equal whatever shares the launch, wherever the buffers lie.  -1 and cv2_last_error, nothing launched, for a
+ * length outside 0 .. 2^30, a missing table or source, a target out of range or a workspace that is too small.
+ * Adding these entry points changed no existing struct and no signature: CV2_ABI_VERSION stays. */
+int cv2_loudness_workspace_bytes(const cv2_wave_seg* segs, int32_t n, size_t* bytes);
+int cv2_loudness_batch(const cv2_wave_seg* segs, const cv2_wave_seg* segs_dev, int32_t n, const float* targets, const float* targets_dev,
+                       const float* filter_dev, float* R_dev, float* lufs_dev, void* ws, size_t ws_bytes, void* stream);
+
 /* =====================================================================================================================
  * Prompt features (the extractor that feeds this path): replaces the reference's
  *   feat_extractor = matcha.utils.audio.mel_spectrogram(n_fft 1920, num_mels 80, sampling_rate 24000, hop_size 480, win_size 1920,
